@@ -37,7 +37,7 @@ sys.path.insert(0, ROOT)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"],
                     help="framewise = the reference's default path (chat.py without --use_sam2_video_branch)")
@@ -68,7 +68,46 @@ def parse():
     ap.add_argument("--tiny", action="store_true", help="plumbing check on a toy architecture (NOT a valid bench)")
     ap.add_argument("--plumbing", action="store_true",
                     help="allow --gpus N with fewer than N devices (ranks share GPUs; VG_DIST_BACKEND=gloo): a plumbing check, NOT a scaling record — the line says so")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (token ids, masks) as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_MASK_SAMPLES = 1 << 21     # mask pixels written by --dump-outputs (24 MB with their float64 indices): all of them when the clip has fewer
+
+
+def dump_outputs(path, out_ids, segs):
+    """--dump-outputs: what inference() returned to its caller in the last timed step, as float32 / float64 .npy files, < 64 MB in all.
+      output_ids.npy          float64 [1, L]     the prompt + generated token ids
+      mask_frames.npy         float64 [T]        the frame indices of the returned masks (the dict's keys, sorted)
+      mask_objects.npy        float64 [N]        the object indices
+      mask_area.npy           float64 [T, N]     pixels set per mask (covers every returned pixel)
+      mask_sample_index.npy   float64 [n]        flat indices into the [T, N, H, W] masks: a fixed sample (seed 0) of n = min(T*N*H*W, 2^21)
+      mask_sample.npy         float32 [n]        the masks at those indices (0 / 1)
+    Inputs and weights are seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    frames = sorted(segs[0])
+    objs = sorted(segs[0][frames[0]]) if frames else []
+    if frames and objs:
+        m = np.stack([np.stack([segs[0][t][k] for k in objs]) for t in frames])
+    else:
+        m = np.zeros((len(frames), len(objs), 0, 0), dtype=bool)
+    flat = m.reshape(-1)
+    if flat.size <= DUMP_MASK_SAMPLES:
+        idx = np.arange(flat.size, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.size, DUMP_MASK_SAMPLES, dtype=np.int64))
+    arrays = {"output_ids": torch.as_tensor(out_ids).cpu().numpy().astype(np.float64),
+              "mask_frames": np.asarray(frames, dtype=np.float64), "mask_objects": np.asarray(objs, dtype=np.float64),
+              "mask_area": m.sum(axis=(2, 3), dtype=np.float64),
+              "mask_sample_index": idx.astype(np.float64), "mask_sample": flat[idx].astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def make_inputs(cfg, args, world, device):
@@ -692,6 +731,7 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt[0])
     out_ids, segs = out
+    dumped = dump_outputs(args.dump_outputs, out_ids, segs) if args.dump_outputs and rank == 0 else None
     n_obj = len(next(iter(segs[0].values()))) if segs[0] else 0      # (a rank's dict holds ITS frames under their global indices)
     shape = (args.frames, args.src, args.objects, args.te)
     strong = args.scaling == "strong"
@@ -729,6 +769,8 @@ def main():
                    "weights": "random-init (synthetic)"},
         "load_s": round(t_load, 1),
     }
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if world > 1:
         # self-verifying multi-GPU record: the backend, who took part, what the collectives moved and how long the issuing stream spent in them
         comm.profile = True

@@ -230,6 +230,20 @@ int vg_decode_step_end(uint64_t* acc, int64_t* tok, int* pos, int* step, const i
                        const void* row, void* hid_all, int D, int dtype, vg_stream_t stream);
 int vg_decode_advance(int64_t* tok, int* pos, int* step, const int64_t* forced, int n_forced, int64_t* hist, int64_t* raw, int cap,
                       const float* cos, const float* sin, float* rope_cs, int half_dim, int inc, vg_stream_t stream);
+/* Sampled decoding (csrc/vg_sample.hip): HF's Temperature -> TopK -> TopP warpers and the draw on one fp32 logits row x[n]
+ *   (n < 2^22), one launch.  params: the 24-byte device block {float T; float p; int k; int pad; uint64 seed} (k = 0: no top-k; p = 1: no top-p).
+ * vg_sample_partial — acc[0] = the drawn entry's packed (ordered value bits, ~index) key, the hand-off vg_argmax_partial leaves, so
+ *   vg_decode_step_end consumes it.  fast_ws == NULL: the general route (one 1024-thread workgroup, any k).  fast_ws != NULL: the fast route
+ *   for 1 <= k <= 64 and n <= 131072 (up to 64 workgroups + a last-arriver merge; tie overflow or another k falls back to the general route
+ *   inside the launch); fast_ws = vg_sample_workspace_ints() int32, zero-filled once, one per stream (its ticket resets itself).  tok != NULL: *tok = the drawn index as well (either may be NULL, not both).  u = (philox4x32_10(key = seed, counter = (*step, 0, 0, 0))[0] >> 8) * 2^-24, or *u_override when not NULL (tests).
+ * vg_sample_survivors — the entries the warpers keep: idx[j] / prob[j] for j < min(*count, cap), in no particular order; *count (zero on entry)
+ *   receives their number.  prob = softmax over the kept entries.
+ * vg_sample_philox — out[i] = philox4x32_10(key = seeds[i], counter = (steps[i], 0, 0, 0))[0]. */
+int vg_sample_workspace_ints(void);
+int vg_sample_partial(const float* x, int n, const void* params, const int* step, const float* u_override, uint64_t* acc, int64_t* tok,
+                      int* fast_ws, vg_stream_t stream);
+int vg_sample_survivors(const float* x, int n, const void* params, int64_t* idx, float* prob, int cap, int* count, vg_stream_t stream);
+int vg_sample_philox(const uint64_t* seeds, const int* steps, int n, uint32_t* out, vg_stream_t stream);
 
 /* vg_decode_layer (r03): everything of a decoder layer behind the q|k|v projection as ONE launch — vg_decode_attention, then
  *   y_o = attn_out . Wo^T + resid (vg_decode_gemv), and when Wgu != NULL also act = SwiGLU(RMSNorm(y_o; norm_w, eps) . Wgu^T) and

@@ -53,6 +53,10 @@ def _sig(lib):
         "vg_decode_step_begin": ([P, P, P, I, I, P, P, P, P, I, P], c_int),
         "vg_argmax_partial": ([P, L, I, P, I, P], c_int),
         "vg_decode_step_end": ([P, P, P, P, P, I, P, P, I, P, P, I, I, P], c_int),
+        "vg_sample_workspace_ints": ([], c_int),
+        "vg_sample_partial": ([P, I, P, P, P, P, P, P, P], c_int),
+        "vg_sample_survivors": ([P, I, P, P, P, I, P, P], c_int),
+        "vg_sample_philox": ([P, P, I, P, P], c_int),
         "vg_mlp3_grouped": ([P, L, L, P, P, P, P, P, P, P, L, L, I, I, I, I, I, I, ctypes.c_uint, P], c_int),
         "vg_decode_layer_roles": ([I, I, I, I, I, I], c_int),
         "vg_decode_layer_flag_ints": ([], c_int64),

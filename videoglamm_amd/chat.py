@@ -35,6 +35,8 @@ def get_args():
     p.add_argument("--prompt_text", type=str, default="")
     p.add_argument("--video", type=str, default="", help="frames directory or .npy clip; asked for interactively when empty (R/chat.py:513)")
     p.add_argument("--max_new_tokens", type=int, default=1024)     # R/chat.py:566
+    p.add_argument("--seed", type=int, default=None, help="torch.manual_seed(N) before the first clip: reproducible sampled decoding")
+    p.add_argument("--greedy", action="store_true", help="decode greedily even when the checkpoint's generation_config sets do_sample")
     return p.parse_args()
 
 
@@ -123,6 +125,10 @@ def main():
     base = args.base_model_type.split("|")[1]
     model, tokenizer = initialize_model_videogptplus(args.llava_version_or_path, args.precision, args.local_rank, args.load_in_8bit,
                                                      args.load_in_4bit, args.use_sam2_video_branch, base, device=f"cuda:{args.local_rank}")
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    if args.greedy:
+        model.generation_config.do_sample = False
     conv_generator = host.ConvGenerator_VideoGPTPlus(args.use_mm_start_end, base)
     enc_preprocessor, sam_preprocessor = host.EncPreprocessor_VideoGPTPlus(), host.SAM_v2_Preprocess()
     while True:

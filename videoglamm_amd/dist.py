@@ -155,6 +155,14 @@ class FrameSharder:
         else:
             self._timed(name, nbytes, lambda: dist.all_gather(list(recv.chunk(self.world)), send, group=self.group))
 
+    def broadcast_seed(self, seed):
+        """rank 0's 64-bit sampling seed on every rank (8 bytes, only when sampling): the replicated decode then draws the same ids everywhere"""
+        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(self.group) == "nccl" else torch.device("cpu")
+        t = torch.tensor([int(seed) - (1 << 64) if int(seed) >= (1 << 63) else int(seed)], dtype=torch.int64, device=dev)
+        src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+        self._timed("seed_broadcast", 8, lambda: dist.broadcast(t, src=src, group=self.group))
+        return int(t.item()) & 0xFFFFFFFFFFFFFFFF
+
     def sync_seg_embeddings(self, emb):
         """all-gather of the [N,256] [SEG] embeddings; every rank adopts rank 0's copy."""
         return self._all_gather(emb, "seg_all_gather")[0]

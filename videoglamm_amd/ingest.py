@@ -73,7 +73,9 @@ def load_state_dict(model_dir, vision_tower=None, image_vision_tower=None, sam2_
         gen_path = os.path.join(model_dir, "generation_config.json")     # HF generate() stops on generation_config's eos ids
         if os.path.exists(gen_path):
             with open(gen_path) as fh:
-                hf["_generation_eos_token_id"] = json.load(fh).get("eos_token_id")
+                gen = json.load(fh)
+            hf["_generation_eos_token_id"] = gen.get("eos_token_id")
+            hf["_generation_config"] = gen
     if not any(k.startswith(IV2_PREFIX) for k in sd):
         vision_tower = vision_tower or (hf or {}).get("mm_vision_tower")
         if not vision_tower:
@@ -257,7 +259,24 @@ def derive_config(sd, hf=None, seg_token_idx=None):
     for k in ("bos_token_id", "pad_token_id"):
         if hf.get(k) is not None:
             cfg[k] = hf[k]
+    cfg["generation"] = generation_settings(hf.get("_generation_config"))
     return cfg
+
+
+# the decoding fields of generation_config.json this build reads, with transformers' GenerationConfig defaults for absent ones
+GENERATION_DEFAULTS = dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0)
+# fields whose non-neutral value asks for a logits processor / warper / search this build does not have (refused when sampling)
+GENERATION_UNSUPPORTED = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, typical_p=1.0, min_p=None, epsilon_cutoff=0.0, eta_cutoff=0.0,
+                              num_beams=1)
+
+
+def generation_settings(gen=None):
+    """generation_config.json (dict or None) -> {do_sample, temperature, top_k, top_p} with HF's defaults (False / 1.0 / 50 / 1.0) for absent
+    fields, plus the unsupported fields the file sets (model.GenerationConfig refuses them when sampling)."""
+    gen = gen or {}
+    out = {k: (gen[k] if gen.get(k) is not None else v) for k, v in GENERATION_DEFAULTS.items()}
+    out.update({k: gen[k] for k in GENERATION_UNSUPPORTED if k in gen})
+    return out
 
 
 def eos_ids(*sources):

@@ -62,6 +62,47 @@ class _Inner:
         return self.image_vision_tower
 
 
+class GenerationConfig:
+    """model.generation_config: the decoding fields of the checkpoint's generation_config.json this build follows (do_sample, temperature,
+    top_k, top_p; HF's defaults when absent) — assignable like model.config.eos_token_id (R/chat.py:305).  The other fields HF would turn into a
+    logits processor or warper keep their neutral values unless the checkpoint sets them; a non-neutral one is refused when sampling."""
+
+    def __init__(self, d=None):
+        from .ingest import GENERATION_DEFAULTS, GENERATION_UNSUPPORTED
+        self.__dict__.update(GENERATION_DEFAULTS)
+        self.__dict__.update(GENERATION_UNSUPPORTED)
+        self.__dict__.update(d or {})
+
+    def __repr__(self):
+        return f"GenerationConfig({self.__dict__})"
+
+
+def resolve_sampling(gc, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
+    """precedence keyword > model.generation_config (which starts as the checkpoint's) -> None (greedy) or vlm.generate's dict(T, k, p, seed).
+    The seed is one draw from `generator` (torch's default CPU generator when None), taken only when sampling: torch.manual_seed(n)
+    reproduces a run, and greedy runs leave the RNG alone."""
+    from .ingest import GENERATION_UNSUPPORTED
+    pick = lambda v, name: getattr(gc, name) if v is None else v
+    if not pick(do_sample, "do_sample"):
+        return None
+    for name, neutral in GENERATION_UNSUPPORTED.items():
+        v = getattr(gc, name, neutral)
+        if v is not None and v != neutral and not (name == "no_repeat_ngram_size" and int(v) <= 0):
+            raise NotImplementedError(f"generation_config.{name} = {v!r}: this build samples with temperature / top_k / top_p only")
+    T, k, p = pick(temperature, "temperature"), pick(top_k, "top_k"), pick(top_p, "top_p")
+    T = 1.0 if T is None else float(T)
+    k = 0 if k is None else int(k)
+    p = 1.0 if p is None else float(p)
+    if not T > 0:      # TemperatureLogitsWarper
+        raise ValueError(f"`temperature` (={T}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
+    if k < 0:          # TopKLogitsWarper
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {k}")
+    if p < 0 or p > 1.0:     # TopPLogitsWarper
+        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {p}")
+    seed = int(torch.empty((), dtype=torch.int64).random_(generator=generator))
+    return dict(T=T, k=k, p=p, seed=seed)
+
+
 class VideoGLaMMForCausalLM:
     def __init__(self, state_dict, config, torch_dtype=torch.bfloat16, device="cuda", use_sam2_video_branch=False,
                  comm=None, **kwargs):
@@ -91,6 +132,9 @@ class VideoGLaMMForCausalLM:
             self.device = torch.device("cuda", torch.cuda.current_device() if self.device.index is None else self.device.index)
             torch.cuda.set_device(self.device)
         self.use_sam2_video_branch = use_sam2_video_branch
+        # HF generate()'s decoding mode: greedy unless the checkpoint's generation_config.json (or the caller) sets do_sample
+        self.generation_config = GenerationConfig(config.get("generation"))
+        self._sampling = None
         self._build(state_dict)
         self.model = _Inner(self)
         self.comm = comm
@@ -122,6 +166,8 @@ class VideoGLaMMForCausalLM:
                                         iv2_origin_num_frames=iv2_origin_num_frames)
         if config is None:
             config = (hf or {}).get("videoglamm_amd") or ingest.derive_config(sd, hf, seg_token_idx)
+        if "generation" not in config:
+            config = dict(config, generation=ingest.generation_settings((hf or {}).get("_generation_config")))
         return cls(sd, config, **kwargs)
 
     def _build(self, sd):
@@ -234,17 +280,25 @@ class VideoGLaMMForCausalLM:
 
     # ------------------------------------------------------------------ inference surface
     def inference(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                  max_new_tokens=32, use_sam2_video_branch=False):
-        """R/model/VideoGLaMM.py:560-596."""
+                  max_new_tokens=32, use_sam2_video_branch=False, **sampling):
+        """R/model/VideoGLaMM.py:560-596.  Keyword-only extras: do_sample / temperature / top_k / top_p (override model.generation_config for
+        this call) and generator (the torch.Generator the sampling seed is drawn from)."""
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             torch.cuda.set_device(self.device)
         if use_sam2_video_branch:
             if self.config.use_sam2:
                 return self.inference_video_branch(images, context_images, images_for_sam, input_ids, resize_list,
-                                                   original_size_list, max_new_tokens)
+                                                   original_size_list, max_new_tokens, **sampling)
             raise ValueError("use_sam2_video_branch is True, but model is not configured to use SAM2")
         return self.inference_framewise(images, context_images, images_for_sam, input_ids, resize_list,
-                                        original_size_list, max_new_tokens)
+                                        original_size_list, max_new_tokens, **sampling)
+
+    def _resolve_sampling(self, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
+        """this call's decoding mode; multi-GPU: every rank adopts rank 0's seed (the decode is replicated and must emit the same ids)"""
+        s = resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator)
+        if s is not None and self.comm is not None and self.comm.world > 1:
+            s["seed"] = self.comm.broadcast_seed(s["seed"])
+        self._sampling = s
 
     def _text_side(self, images, context_images, input_ids, max_new_tokens, after_prefill=None):
         assert len(images) == 1 and input_ids.shape[0] == 1  # batch size is 1 (VideoGLaMM.py:252-253)
@@ -253,7 +307,7 @@ class VideoGLaMMForCausalLM:
         out_ids, emb = generate(self.P, self._live_cfg(), self.towers, images[0].to(self.device), None if ctx is None else ctx.to(self.device),
                                 input_ids[0].cpu(), max_new_tokens, self._eos(),
                                 token_hook=self.token_hook, after_prefill=after_prefill, comm=self.comm,
-                                trace=self.capture, stages=self.stages)
+                                trace=self.capture, stages=self.stages, sampling=self._sampling)
         if self.capture is not None:
             self.capture["emb"] = emb
         return out_ids.unsqueeze(0), emb
@@ -340,8 +394,9 @@ class VideoGLaMMForCausalLM:
         return feats, join
 
     def inference_framewise(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                            max_new_tokens=32):
+                            max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
         """R/model/VideoGLaMM.py:598-768 -> (output_ids [1,L+G], [ {frame: {obj: mask}} ])."""
+        self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens)
         if emb.shape[0] == 0:
@@ -365,8 +420,9 @@ class VideoGLaMMForCausalLM:
         return out_ids, [self._segments(masks)]
 
     def inference_video_branch(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                               max_new_tokens=32):
+                               max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
         """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842)."""
+        self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         # multi-GPU: frames shard for Hiera only (the propagation is a recurrence over frames) and every rank needs every frame's features:
         # one exchange of the whole clip after the last frame (default), or — FrameSharder(stream_features=True) — streamed chunk by chunk on a

@@ -732,6 +732,67 @@ def argmax_partial(x, acc):
     _lib.check(lib.vg_argmax_partial(_p(x), 1, x.numel(), _p(acc), _dt(x), _stream()), "vg_argmax_partial")
 
 
+def sampling_params(T, k, p, seed, device, out=None):
+    """the 24-byte device parameter block vg_sample reads ({float T; float p; int k; int pad; uint64 seed}) as int32 [6]; `out` is rewritten in
+    place (one host-to-device copy, outside any capture), so a captured decode step picks the new values up without a re-capture."""
+    import struct
+    raw = struct.pack("<ffiiQ", float(T), float(p), int(k), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    host = torch.frombuffer(bytearray(raw), dtype=torch.int32)
+    if out is None:
+        out = torch.empty(6, dtype=torch.int32, device=device)
+    out.copy_(host)
+    return out
+
+
+def sample_workspace(device):
+    """the fast sampling route's workspace (vg_sample_workspace_ints() int32, zero-filled; one per stream, reused by every launch)"""
+    return torch.zeros(int(_lib.load().vg_sample_workspace_ints()), dtype=torch.int32, device=device)
+
+
+def sample_fast_route(k, n):
+    """whether vg_sample_partial's fast route covers top_k = k on a row of n entries"""
+    return 1 <= int(k) <= 64 and int(k) < n and n <= 131072
+
+
+def sample_partial(x, params_dev, step_dev, acc=None, tok=None, u_override=None, fast_ws=None):
+    """HF's Temperature -> TopK -> TopP warpers + the draw on one fp32 logits row (vg_sample_partial): the drawn entry's packed key into acc
+    (int64 [1], decode_step_end's hand-off) and / or its index into tok (int64 [1]).  u_override: device float32 [1] replacing the Philox uniform.
+    fast_ws (sample_workspace): the multi-workgroup route for 1 <= k <= 64 (same results; other k fall back inside the launch); None: general route."""
+    lib = _lib.load()
+    x = x.contiguous().view(-1)
+    assert x.dtype == torch.float32 and params_dev.dtype == torch.int32 and params_dev.numel() == 6 and step_dev.dtype == torch.int32
+    assert acc is not None or tok is not None
+    assert all(t is None or t.dtype == torch.int64 for t in (acc, tok)) and (u_override is None or u_override.dtype == torch.float32)
+    assert fast_ws is None or (fast_ws.dtype == torch.int32 and fast_ws.numel() >= lib.vg_sample_workspace_ints())
+    rc = lib.vg_sample_partial(_p(x), x.numel(), _p(params_dev), _p(step_dev), _p(u_override), _p(acc), _p(tok), _p(fast_ws), _stream())
+    _lib.check(rc, "vg_sample_partial")
+
+
+def sample_survivors(x, params_dev):
+    """the entries the warpers keep for one fp32 logits row (vg_sample_survivors) -> (indices int64, probabilities fp32), ascending index."""
+    lib = _lib.load()
+    x = x.contiguous().view(-1)
+    assert x.dtype == torch.float32 and params_dev.dtype == torch.int32 and params_dev.numel() == 6
+    n = x.numel()
+    idx = torch.empty(n, dtype=torch.int64, device=x.device)
+    prob = torch.empty(n, dtype=torch.float32, device=x.device)
+    count = torch.zeros(1, dtype=torch.int32, device=x.device)
+    _lib.check(lib.vg_sample_survivors(_p(x), n, _p(params_dev), _p(idx), _p(prob), n, _p(count), _stream()), "vg_sample_survivors")
+    m = int(count)
+    idx, prob = idx[:m].cpu(), prob[:m].cpu()
+    order = torch.argsort(idx)
+    return idx[order], prob[order]
+
+
+def philox(seeds, steps):
+    """word 0 of philox4x32_10(key = seeds[i], counter = (steps[i], 0, 0, 0)) (vg_sample_philox): seeds int64 / steps int32 device tensors."""
+    lib = _lib.load()
+    assert seeds.dtype == torch.int64 and steps.dtype == torch.int32 and seeds.numel() == steps.numel()
+    out = torch.empty(seeds.numel(), dtype=torch.int32, device=seeds.device)
+    _lib.check(lib.vg_sample_philox(_p(seeds.contiguous()), _p(steps.contiguous()), seeds.numel(), _p(out), _stream()), "vg_sample_philox")
+    return out
+
+
 def decode_step_end(acc, tok_dev, pos_dev, step_dev, row, hid_all, forced=None, hist=None, raw=None):
     """the tail of a captured decode step (vg_decode_step_end): token from the argmax accumulator, final-norm row into hid_all[*pos], bookkeeping, *pos += 1."""
     lib = _lib.load()

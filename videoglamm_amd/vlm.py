@@ -234,11 +234,31 @@ class LlamaDecoder:
         self.rope_path = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
                           and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
         self.kpw2 = int(os.environ.get("VG_DEC2_KPW", "256"))
+        # sampled decoding (vg_sample): None = greedy; else dict(T, k, p, seed), the values held in the device block samp_params that
+        # the captured step reads — a new temperature / top-p / top-k / seed is a copy into it, never a re-capture
+        self.sampling, self.samp_params, self.samp_ws, self.samp_fast = None, None, None, False
 
     def reset(self):
         self.pos = 0
         self.pos_dev.zero_()
         self.step_dev.zero_()
+        # a step that stopped between the token hand-off and its decode (an exception in a hook, an aborted clip) must not leave its key or its
+        # forcing table to the next clip
+        self.amax_acc.zero_()
+        self.forced.fill_(-1)
+
+    def set_sampling(self, sampling):
+        """sampling = None (greedy) or dict(T=, k=, p=, seed=): HF's Temperature / TopK / TopP warpers and a Philox draw per step (ops.sample_partial)"""
+        if sampling is None:
+            self.sampling = None
+            return
+        if self.samp_params is None:
+            self.samp_params = torch.zeros(6, dtype=torch.int32, device=self.P.device)
+            self.samp_ws = ops.sample_workspace(self.P.device)
+        self.sampling = dict(T=float(sampling["T"]), k=int(sampling["k"]), p=float(sampling["p"]), seed=int(sampling["seed"]))
+        ops.sampling_params(self.sampling["T"], self.sampling["k"], self.sampling["p"], self.sampling["seed"], self.P.device, out=self.samp_params)
+        # the route is fixed by k: the multi-workgroup fast route for 1 <= k <= 64, the one-workgroup general route otherwise
+        self.samp_fast = ops.sample_fast_route(self.sampling["k"], self.P.t("lm_head.weight").shape[0])
 
     def _layers(self, x, pos0, pos_dev, kv_hook=None):
         """decoder stack on x [S,D]; KV appended at pos (host value pos0, or *pos_dev when given).
@@ -390,11 +410,14 @@ class LlamaDecoder:
         return last
 
     def next_token(self, hidden_row):
-        """lm_head + argmax of one final-norm row -> tok_dev (device int64[1])."""
+        """lm_head + argmax (or, sampling, the warpers + the draw of step *step_dev) of one final-norm row -> tok_dev (device int64[1])."""
         if self.w8 and hidden_row.shape[0] == 1:
             logits = ops.decode_gemv_w8(hidden_row.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(hidden_row, self.P.w("lm_head"), out_dtype=torch.float32)
+        if self.sampling is not None:
+            ops.sample_partial(logits[-1], self.samp_params, self.step_dev, tok=self.tok_dev, fast_ws=self.samp_ws if self.samp_fast else None)
+            return
         ops.argmax(logits.view(1, -1), out=self.tok_dev)
 
     def _decode_step(self):
@@ -414,7 +437,11 @@ class LlamaDecoder:
             logits = ops.decode_gemv_w8(h.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(h, self.P.w("lm_head"), out_dtype=torch.float32)
-        ops.argmax_partial(logits.view(-1), self.amax_acc)
+        if self.sampling is not None:
+            ops.sample_partial(logits.view(-1), self.samp_params, self.step_dev, acc=self.amax_acc,     # the same hand-off as argmax_partial
+                               fast_ws=self.samp_ws if self.samp_fast else None)
+        else:
+            ops.argmax_partial(logits.view(-1), self.amax_acc)
         ops.decode_step_end(self.amax_acc, self.tok_dev, self.pos_dev, self.step_dev, h, self.hid_all, self.forced, self.hist, self.raw)
 
     def advance(self, inc):
@@ -434,7 +461,9 @@ class LlamaDecoder:
         # long caches: two 64-key blocks per decode-attention workgroup (half the partials to publish, arrive and merge: the merge of a C2 prompt's
         # 54 splits took two passes); a launch parameter, so each setting has its own captured graph.  VG_DEC_KPW_MIN = first position that uses it
         self.kpw = 128 if (self.pos >= self.kpw_min and not self.rope_path) else 0
-        self.graph = self.graphs.get(self.kpw)
+        # the route (greedy / fast / general sampler) is part of the captured launches; T, k, p and the seed are not
+        key = self.kpw if self.sampling is None else (self.kpw, "sample_fast" if self.samp_fast else "sample")
+        self.graph = self.graphs.get(key)
         if not self.use_graph:
             self._decode_step()
         else:
@@ -451,7 +480,7 @@ class LlamaDecoder:
                 # finished collectives; under the default (global) mode such a call from another thread can invalidate the capture
                 with ops.graph_capture(g):      # (thread-local capture mode, cyclic GC held off: ops.graph_capture)
                     self._decode_step()
-                self.graph = self.graphs[self.kpw] = g
+                self.graph = self.graphs[key] = g
                 self.tok_dev.copy_(snap_tok)
                 self.pos_dev.copy_(snap_pos)
                 self.step_dev.copy_(snap_step)
@@ -485,7 +514,7 @@ def stage_mark(stages, name):
 
 
 def generate(params, cfg, towers, images, context_images, input_ids, max_new_tokens, eos_token_id=None, visual=None,
-             token_hook=None, after_prefill=None, comm=None, trace=None, stages=None):
+             token_hook=None, after_prefill=None, comm=None, trace=None, stages=None, sampling=None):
     """Steps A–D of VideoGLaMM_SAM2.inference_* (R/model/VideoGLaMM.py:609-655 / 781-831) with encode-once +
     KV-cache scheduling.  The hidden state the reference gathers for a [SEG] at output position p is the
     final-norm state of position p-1 = the row that produced the token, captured here as it is
@@ -494,6 +523,8 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     benchmark, whose random weights never emit [SEG] — no work is skipped).
     trace: optional dict; trace["argmax"] receives the model's own argmax of every step (before any forcing).
     eos_token_id: one id or several (HF generate() stops on any id of generation_config.eos_token_id).
+    sampling: None = greedy; dict(T=, k=, p=, seed=) = HF's do_sample decoding (Temperature -> TopK -> TopP, then a draw) on the device,
+    token j drawn with the uniform of Philox counter j; trace["argmax"] then holds the drawn ids before forcing.
     input_ids: host int64 [L] -> (output_ids host int64 [L+G], pred_embeddings device [N,256])."""
     seg_idx = cfg["seg_token_idx"]
     eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(e) for e in eos_token_id})
@@ -508,6 +539,7 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
         dec = LlamaDecoder(params, cfg["llm"], -(-need // 1024) * 1024)
         params._decoder = dec          # KV cache + captured decode graph are reused across clips
     dec.reset()
+    dec.set_sampling(sampling)
     if comm is not None and comm.world > 1 and x.shape[0] >= 64 * comm.world and os.environ.get("VG_PREFILL_SHARDED", "0") == "1":
         hidden = dec.forward_sharded(x, comm)   # opt-in sequence-parallel prefill: 1/world of the rows per rank (row chunks of another
         #                                         M take other GEMM routes: bf16 ids may differ from the single-GPU run; default = replicated)

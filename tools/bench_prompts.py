@@ -1,0 +1,106 @@
+"""Several prompts about one clip: model.inference_prompts() against the same prompts as sequential inference() calls.
+
+Workload: BASELINE config C2 (synthetic Llama-3-8B, 16 encoder frames, 32 x 1024^2 SAM frames, 32 new tokens, [SEG] forced at step 8 as
+bench.py does) and the same clip with the Phi-3-mini LLM (--llm).  The prompts share bench.py's prefix ([1, 5, 6] + the visual block) and
+differ in their 30 question ids.  One JSON line per LLM:
+  "prompts_ms"[B]:    ms per inference_prompts() call with B prompts
+  "sequential_ms"[B]: ms for the same B prompts as B inference() calls
+  "ratio"[B]:         prompts_ms / sequential_ms
+  "decode_step_ms":   one replayed decode step of one prompt (LlamaDecoder.decode_step, the step every prompt decodes with), ms per token
+--out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
+
+    python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from videoglamm_amd import synth  # noqa: E402
+from videoglamm_amd.model import VideoGLaMMForCausalLM  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1000.0 / steps
+
+
+def decode_step_ms(model, tokens=64):
+    """replayed decode steps of the cached decoder, continuing from where the last call left it (rows past the clip: scratch)"""
+    dec = model.P._decoder
+    tokens = min(tokens, dec.max_len - dec.pos - 3)
+    if tokens < 2:
+        return None
+    for _ in range(2):                 # settle (and capture, should this position range need a graph of its own)
+        dec.decode_step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(tokens - 1):
+        dec.decode_step()
+    e1.record()
+    e1.synchronize()
+    return round(e0.elapsed_time(e1) / (tokens - 1), 4)
+
+
+def run(llm, args, device):
+    cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
+    cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
+    sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
+    model = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, cfg, torch_dtype=torch.bfloat16, device=device))
+    g = torch.Generator().manual_seed(1234)
+    te, S = 16, cfg["sam2"]["image_size"]
+    iv, cl = cfg["iv2"]["img_size"], cfg["clip"]["img_size"]
+    images = [torch.randn(te, 3, iv, iv, generator=g).to(device)]
+    context = [torch.randn(te, 3, cl, cl, generator=g).to(device)]
+    sam = [torch.randn(args.frames, 3, S, S, generator=g).to(device)]
+    head = torch.cat([torch.tensor([1, 5, 6]), torch.full((te,), -200)])
+    prompts = [torch.cat([head, torch.randint(3, cfg["llm"]["vocab"] - 2, (30,), generator=g)]) for _ in range(max(args.batches))]
+    rest = ([(1024, 1024)], [(args.src, args.src)])
+    video = args.branch == "video"
+    rec = dict(llm=llm, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, prompts_ms={}, sequential_ms={}, ratio={})
+    for B in args.batches:
+        P = prompts[:B]
+        seq = timed(lambda: [model.inference(images, context, sam, x[None], *rest, args.max_new_tokens, video) for x in P], args.steps, args.warmup)
+        bat = timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video), args.steps, args.warmup)
+        rec["prompts_ms"][B], rec["sequential_ms"][B], rec["ratio"][B] = round(bat, 2), round(seq, 2), round(bat / seq, 3)
+    rec["decode_step_ms"] = decode_step_ms(model)
+    del model, sd
+    torch.cuda.empty_cache()
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--llm", nargs="+", default=["llama3-8b", "phi3-mini"], choices=["llama3-8b", "phi3-mini"])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8])
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--src", type=int, default=1024)
+    ap.add_argument("--max-new-tokens", type=int, default=32)
+    ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    torch.set_grad_enabled(False)
+    device = torch.device("cuda", 0)
+    for llm in args.llm:
+        line = json.dumps(run(llm, args, device))
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

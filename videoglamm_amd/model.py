@@ -462,3 +462,92 @@ class VideoGLaMMForCausalLM:
         if self.capture is not None:
             self.capture["logits"] = logits
         return out_ids, [self._segments(self._to_host(self._binarize(logits)))]
+
+    # ------------------------------------------------------------------ several prompts about one clip
+    def inference_prompts(self, images, context_images, images_for_sam, input_ids_list, resize_list, original_size_list,
+                          max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
+                          generator=None):
+        """B prompts ([1, L_b] or [L_b] each) about ONE clip -> (output ids [1, L_b + G_b] per prompt, {frame: {obj: mask}} per prompt).
+        Entry b means what inference(..., input_ids=input_ids_list[b]) means; a prompt without a [SEG] gets {} (as the video branch does,
+        R/model/VideoGLaMM.py:840-842).  The towers, Hiera and the prefill of the shared prefix (system text + visual block, identical ids in
+        every prompt) run once; SAM2 runs once with every prompt's [SEG] embeddings as its objects.  Sampling draws one seed per prompt from
+        `generator`, in list order.  More than 16 prompts run in consecutive groups of 16."""
+        from .prompts import GROUP, check_prompts
+        if self.comm is not None and self.comm.world > 1:
+            raise NotImplementedError("inference_prompts() runs on one GPU: call inference() per prompt on a multi-GPU model")
+        ids_list = [torch.as_tensor(x).cpu().long() for x in input_ids_list]
+        if not ids_list:
+            raise NotImplementedError("inference_prompts() needs at least one prompt")
+        for b, ids in enumerate(ids_list):
+            if ids.dim() == 2:
+                assert ids.shape[0] == 1, f"input_ids_list[{b}]: one prompt per entry ([1, L] or [L])"
+                ids_list[b] = ids = ids[0]
+            assert ids.dim() == 1, f"input_ids_list[{b}]: one prompt per entry ([1, L] or [L])"
+        assert len(images) == 1  # one clip (VideoGLaMM.py:252-253)
+        if use_sam2_video_branch and not self.config.use_sam2:
+            raise ValueError("use_sam2_video_branch is True, but model is not configured to use SAM2")
+        check_prompts(ids_list)
+        if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
+            torch.cuda.set_device(self.device)
+        samplings = [resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator) for _ in ids_list]
+        out_ids, segs = [], []
+        for g in range(0, len(ids_list), GROUP):
+            o, s = self._prompts_group(images, context_images, images_for_sam, ids_list[g:g + GROUP], original_size_list, max_new_tokens,
+                                       use_sam2_video_branch, samplings[g:g + GROUP])
+            out_ids += o
+            segs += s
+        return out_ids, segs
+
+    def _prompts_group(self, images, context_images, images_for_sam, ids_list, original_size_list, max_new_tokens, video, samplings):
+        from .prompts import generate_prompts
+        sam = images_for_sam[0].to(self.device)
+        graphed = video and self.device.type == "cuda" and os.environ.get("VG_VIDEO_GRAPH", "1") == "1"
+        bufs = self.sam2.video_static_feats(sam.shape[0]) if graphed else None
+        box = {}
+
+        def start():
+            box["feats"], box["join"] = self._hiera_async(sam, bufs=bufs)
+
+        # VG_HIERA_START as in _text_and_hiera: "first" (default) puts Hiera on the side stream before the towers, "prefill" after the prefix's
+        # prefill, "serial" runs it alone first (per-stage timing)
+        mode = os.environ.get("VG_HIERA_START", "first")
+        if mode == "serial":
+            stage_mark(self.stages, "begin")
+            feats = self.sam2.hiera_frames(sam, bufs=bufs)
+            stage_mark(self.stages, "hiera_fpn")
+            box["join"] = lambda: None
+        elif mode == "first":
+            start()
+        ctx = context_images[0] if context_images is not None else None
+        traces = [{} for _ in ids_list] if self.capture is not None else None
+        out, emb, counts = generate_prompts(self.P, self._live_cfg(), self.towers, images[0].to(self.device),
+                                            None if ctx is None else ctx.to(self.device), ids_list, max_new_tokens, self._eos(),
+                                            token_hook=self.token_hook, samplings=samplings, traces=traces,
+                                            after_prefix=start if mode not in ("serial", "first") else None, stages=self.stages)
+        box["join"]()
+        if mode != "serial":
+            feats = box["feats"]
+        out = [o.unsqueeze(0) for o in out]
+        starts = [sum(counts[:b]) for b in range(len(counts))]
+        if self.capture is not None:
+            self.capture["argmax"] = [t.get("argmax", []) for t in traces]
+            self.capture["emb"] = [emb[a:a + n] for a, n in zip(starts, counts)]
+        if emb.shape[0] == 0:
+            return out, [{} for _ in ids_list]
+        hw = tuple(original_size_list[0])
+        fast = self._fast_masks()
+        if video:
+            if graphed:
+                res = self.sam2.video_branch_graphed(sam, emb, hw, feats, as_masks=fast)
+            else:
+                res = self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=fast)
+        else:
+            res = self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=fast)[0]
+        if not fast:
+            if self.capture is not None:
+                self.capture["logits"] = [res[:, a:a + n] for a, n in zip(starts, counts)]
+            res = self._binarize(res)
+        host = self._to_host(res)
+        stage_mark(self.stages, "propagation" if video else "mask_decode")
+        # objects [a, a + n) are prompt b's, renumbered from 0
+        return out, [self._segments(host[:, a:a + n]) if n else {} for a, n in zip(starts, counts)]

@@ -553,6 +553,25 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     if after_prefill is not None:
         after_prefill()   # e.g. enqueue the (LLM-independent, MFMA-bound) Hiera pass on a side stream so that it
         #                   overlaps the HBM-bound decode loop below
+    decode_loop(params, dec, ids, max_new_tokens, eos, token_hook, trace)
+    out_ids = torch.tensor(ids, dtype=torch.int64)
+    # seg_token_mask = (output_ids[:,1:] == seg) left-padded by `added` (VideoGLaMM.py:630-633,803-806):
+    # the row picked for a [SEG] at output position j is j-1+added, i.e. the state that emitted it
+    rows = [j - 1 + added for j in range(1, len(ids)) if ids[j] == seg_idx]
+    if not rows:
+        stage_mark(stages, "decode")
+        return out_ids, torch.empty(0, 256, dtype=params.dtype, device=params.device)
+    h = dec.hid_all[torch.tensor(rows, device=params.device)]
+    fc = "model.text_hidden_fcs.0."
+    h = ops.linear(h, params.w(fc + "0"), params.b(fc + "0"), act=ops.ACT_RELU)
+    emb = ops.linear(h, params.w(fc + "2"), params.b(fc + "2"))
+    stage_mark(stages, "decode")
+    return out_ids, emb
+
+
+def decode_loop(params, dec, ids, max_new_tokens, eos, token_hook=None, trace=None):
+    """generate()'s token loop from the token the prefill emitted (dec.next_token already enqueued): appends the emitted ids to the host list
+    `ids` until an id of `eos` or max_new_tokens; dec's hid_all then holds the final-norm row of every decoded position."""
     # The loop.  Forcing / recording / the position bump can happen on the device (LlamaDecoder.advance), so with no Python hook in the way step k + 1
     # can be enqueued BEFORE token k is read back (VG_DECODE_AHEAD=1: tokens return on a side stream behind per-step events; the step launched while
     # an EOS token was in flight is wasted — it writes cache rows past the end that nobody reads).  Built for VERDICT r05 item 1(c) and measured r06 on C2
@@ -618,16 +637,3 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     if dec.chain_roles and dec.chain_flags is not None and int(dec.chain_err) + int(dec.chain_flags[:, 1].sum()):
         # VG_DECODE_CHAIN: a workgroup of a chained layer launch stopped waiting for its producer role (bounded wait) — the ids above are not to be trusted
         raise ops._lib.VGKernelError("vg_decode_layer: a device-side wait gave up (flags[1] set); rerun with VG_DECODE_CHAIN=0")
-    out_ids = torch.tensor(ids, dtype=torch.int64)
-    # seg_token_mask = (output_ids[:,1:] == seg) left-padded by `added` (VideoGLaMM.py:630-633,803-806):
-    # the row picked for a [SEG] at output position j is j-1+added, i.e. the state that emitted it
-    rows = [j - 1 + added for j in range(1, len(ids)) if ids[j] == seg_idx]
-    if not rows:
-        stage_mark(stages, "decode")
-        return out_ids, torch.empty(0, 256, dtype=params.dtype, device=params.device)
-    h = dec.hid_all[torch.tensor(rows, device=params.device)]
-    fc = "model.text_hidden_fcs.0."
-    h = ops.linear(h, params.w(fc + "0"), params.b(fc + "0"), act=ops.ACT_RELU)
-    emb = ops.linear(h, params.w(fc + "2"), params.b(fc + "2"))
-    stage_mark(stages, "decode")
-    return out_ids, emb

@@ -230,6 +230,31 @@ int vg_decode_step_end(uint64_t* acc, int64_t* tok, int* pos, int* step, const i
                        const void* row, void* hid_all, int D, int dtype, vg_stream_t stream);
 int vg_decode_advance(int64_t* tok, int* pos, int* step, const int64_t* forced, int n_forced, int64_t* hist, int64_t* raw, int cap,
                       const float* cos, const float* sin, float* rope_cs, int half_dim, int inc, vg_stream_t stream);
+/* The batched multi-prompt decode step: B <= 16 rows, each bit-identical to the single-row kernel on that row alone.
+ * vg_decode_rows_supported: 1 when the B-row kernels below cover a bf16 Llama layer of this shape (head_dim 128; hidden / inter multiples of 2048).
+ * vg_decode_gemv_rows: vg_decode_gemv for B rows x[b] = x + b * ldx -> y + b * ldy (residual R + b * ldr); bf16 only.
+ * vg_decode_qkv_rope_rows: vg_decode_qkv_rope for B rows: row b at position pos[b] with rope_cs + b * D (cos row | sin row), q -> q_out + b * ldq,
+ *   its key / value rows into slot b: k_slots / v_slots + b * slot_stride + (pos[b] - row0) * Hkv * D (rows clamped to [0, slot_rows)).
+ * vg_decode_attention2_rows: vg_decode_attention2 for B rows (q / out rows of H * D); key rows below row0 (a multiple of keys_per_wg) from
+ *   k_cache / v_cache ([max_len, Hkv, D], shared), rows from row0 on from slot b as above.  n_bound: every pos[b] < n_bound <= row0 + slot_rows over
+ *   the launches (the grid's splits).  workspace: vg_decode_attention2_rows_ws_floats() floats, zero-filled once.
+ * vg_decode_step_begin_rows / vg_decode_step_end_rows: vg_decode_step_begin / vg_decode_step_end per row b: tok / pos / step / acc [b], x / row + b * D,
+ *   rope_cs + b * 2 * half_dim, forced / hist / raw + b * n_forced / cap, final-norm row of position p into hid + b * hid_stride + (p - hid_row0) * D
+ *   (rows clamped to [0, hid_rows)). */
+int vg_decode_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype);
+int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
+                        const void* R, int64_t ldr, int N, int K, int B, int glu, int dtype, vg_stream_t stream);
+int vg_decode_qkv_rope_rows(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, int64_t ldq,
+                            void* k_slots, void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* rope_cs, const int* pos,
+                            int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream);
+int64_t vg_decode_attention2_rows_ws_floats(int H, int Hkv, int D, int n_bound, int keys_per_wg, int B);
+int vg_decode_attention2_rows(const void* q, const void* k_cache, const void* v_cache, int max_len, const void* k_slots, const void* v_slots,
+                              int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D, int n_bound, int window, float scale,
+                              const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg, int B, int dtype, vg_stream_t stream);
+int vg_decode_step_begin_rows(const int64_t* tok, const void* table, void* x, int D, int dtype, const int* pos, const float* cos, const float* sin,
+                              float* rope_cs, int half_dim, int B, vg_stream_t stream);
+int vg_decode_step_end_rows(uint64_t* acc, int64_t* tok, int* pos, int* step, const int64_t* forced, int n_forced, int64_t* hist, int64_t* raw,
+                            int cap, const void* row, void* hid, int64_t hid_stride, int hid_row0, int hid_rows, int D, int dtype, int B, vg_stream_t stream);
 /* Sampled decoding (csrc/vg_sample.hip): HF's Temperature -> TopK -> TopP warpers and the draw on one fp32 logits row x[n]
  *   (n < 2^22), one launch.  params: the 24-byte device block {float T; float p; int k; int pad; uint64 seed} (k = 0: no top-k; p = 1: no top-p).
  * vg_sample_partial — acc[0] = the drawn entry's packed (ordered value bits, ~index) key, the hand-off vg_argmax_partial leaves, so

@@ -6,10 +6,12 @@ differ in their 30 question ids.  One JSON line per LLM:
   "prompts_ms"[B]:    ms per inference_prompts() call with B prompts
   "sequential_ms"[B]: ms for the same B prompts as B inference() calls
   "ratio"[B]:         prompts_ms / sequential_ms
-  "decode_step_ms":   one replayed decode step of one prompt (LlamaDecoder.decode_step, the step every prompt decodes with), ms per token
+  "decode_step_ms":   one replayed decode step of one prompt (LlamaDecoder.decode_step, the step the sequential loop decodes with), ms per token
+  "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode; Llama-3 width only), ms per step
+--ab also times inference_prompts() with VG_PROMPTS_BATCHED=0 ("prompts_seq_ms"[B]: the prompts decoded one after another).
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 
-    python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise] [--out FILE]
+    python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise] [--ab] [--out FILE]
 """
 import argparse
 import json
@@ -53,6 +55,26 @@ def decode_step_ms(model, tokens=64):
     return round(e0.elapsed_time(e1) / (tokens - 1), 4)
 
 
+def rows_step_ms(model, tokens=32):
+    """replayed steps of the batched state the last inference_prompts() call left, every row restarted at the position it was loaded at (the end
+    of its suffix): the steps attend as many keys as the first steps of the real loop and overwrite only that loop's own decode rows"""
+    rows = next(iter(getattr(model.P._decoder, "_rows", {}).values()), None)
+    if rows is None:
+        return None
+    tokens = min(tokens, rows.n_bound - max(rows.start_pos) - 2)
+    rows.set_positions(rows.start_pos)
+    for _ in range(2):
+        rows.decode_step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(tokens - 1):
+        rows.decode_step()
+    e1.record()
+    e1.synchronize()
+    return round(e0.elapsed_time(e1) / (tokens - 1), 4)
+
+
 def run(llm, args, device):
     cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
@@ -68,12 +90,23 @@ def run(llm, args, device):
     prompts = [torch.cat([head, torch.randint(3, cfg["llm"]["vocab"] - 2, (30,), generator=g)]) for _ in range(max(args.batches))]
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
-    rec = dict(llm=llm, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, prompts_ms={}, sequential_ms={}, ratio={})
+    rec = dict(llm=llm, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, prompts_ms={}, sequential_ms={}, ratio={},
+               rows_step_ms={})
+    if args.ab:
+        rec["prompts_seq_ms"] = {}
     for B in args.batches:
         P = prompts[:B]
         seq = timed(lambda: [model.inference(images, context, sam, x[None], *rest, args.max_new_tokens, video) for x in P], args.steps, args.warmup)
         bat = timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video), args.steps, args.warmup)
         rec["prompts_ms"][B], rec["sequential_ms"][B], rec["ratio"][B] = round(bat, 2), round(seq, 2), round(bat / seq, 3)
+        rec["rows_step_ms"][B] = rows_step_ms(model) if B > 1 else None
+        if args.ab:
+            os.environ["VG_PROMPTS_BATCHED"] = "0"
+            try:
+                rec["prompts_seq_ms"][B] = round(timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video),
+                                                       args.steps, args.warmup), 2)
+            finally:
+                os.environ.pop("VG_PROMPTS_BATCHED")
     rec["decode_step_ms"] = decode_step_ms(model)
     del model, sd
     torch.cuda.empty_cache()
@@ -90,6 +123,7 @@ def main():
     ap.add_argument("--src", type=int, default=1024)
     ap.add_argument("--max-new-tokens", type=int, default=32)
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
+    ap.add_argument("--ab", action="store_true", help="also time inference_prompts() on the sequential loop (VG_PROMPTS_BATCHED=0)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)

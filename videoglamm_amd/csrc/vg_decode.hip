@@ -497,6 +497,246 @@ extern "C" int vg_decode_qkv_rope(const void* x, const void* Wqkv, int64_t ldw, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// B-row forms of vg_decode_gemv / vg_decode_qkv_rope (the batched multi-prompt decode step): one weight pair is loaded once and applied
+// to the BR rows of x.  Every row sees exactly the single-row kernel's arithmetic: the same RMSNorm prologue (256 threads, XN chunks per thread, wave
+// sums, the 4-wave total), the same lane -> chunk walk (batch cb, chunk u: lane + 64 u + 256 cb) with one fp32 accumulator per (row, pair row) fed
+// dec_dot in that order, the same wave_sum and the same epilogue — so row r of the result is bit-identical to vg_decode_gemv on row r alone.
+// Which wave owns which pair does not enter the sums (the split is free).  x is staged into LDS as bf16 rows; when B x K x 2 bytes exceed the
+// budget the K batches are staged in phases and each wave owns one pair, its accumulators carried across the phases (the order stays).
+constexpr int DEC_ROWS_PPW = 8, DEC_ROWS_LDS = 64 * 1024;
+
+struct DecRowsArgs {
+  const void* x; int64_t ldx; const void* W; int64_t ldw; void* y; int64_t ldy; const float* nw; float eps; const void* R; int64_t ldr;
+  int N, K, B, ppw, nph;
+  // RoPE form: rope_cs [B][2][RHD] fp32, pos [B]; row r's key / value rows go to slot r: kc + r * slot_stride + (pos[r] - row0) * Hkv * 2 RHD
+  const float* rope_cs; const int* pos; void* kc; void* vc; int64_t slot_stride; int row0, slot_rows, H, Hkv;
+};
+
+template <typename TO, bool GLU, int NB, int BR, int RHD>
+__global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
+  typedef bf16_t T;
+  constexpr int CPB = 4, KPC = 8, NWV = 2;
+  constexpr int NCH = NB * CPB * 64, XN = NCH / 256;
+  extern __shared__ __attribute__((aligned(16))) char dec_smem[];
+  __shared__ float red[BR][4];
+  __shared__ float res[4][DEC_ROWS_PPW][BR][2];
+  u32x4_t* xs = (u32x4_t*)dec_smem;                // [BR][nph * 256] chunks of the current phase
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int npair = RHD > 0 ? p.N / 2 : GLU ? p.N : (p.N + 1) / 2;
+  const int p0 = (blockIdx.x * 4 + wave) * p.ppw;
+  const int np = max(min(p0 + p.ppw, npair) - p0, 0);
+  const T* W = (const T*)p.W;
+  const int pch = p.nph * 256;                     // chunks per row per phase
+
+  float rstd[BR];
+#pragma unroll
+  for (int r = 0; r < BR; ++r) rstd[r] = 1.f;
+  if (p.nw) {                                      // the norm needs the whole row: the launcher keeps nph = NB
+#pragma unroll
+    for (int r = 0; r < BR; ++r) {
+      const u32x4_t* xg = (const u32x4_t*)((const T*)p.x + (int64_t)min(r, p.B - 1) * p.ldx);
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < XN; ++i) {
+        float f[KPC];
+        dec_unpack<T>(xg[tid + 256 * i], f);
+#pragma unroll
+        for (int e = 0; e < KPC; ++e) ss += f[e] * f[e];
+      }
+      ss = wave_sum(ss);
+      if (lane == 0) red[r][wave] = ss;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < BR; ++r) rstd[r] = rsqrtf((red[r][0] + red[r][1] + red[r][2] + red[r][3]) / (float)p.K + p.eps);
+  }
+
+  float a0[BR], a1[BR];
+#pragma unroll
+  for (int r = 0; r < BR; ++r) { a0[r] = 0.f; a1[r] = 0.f; }
+  for (int ph = 0; ph < NB; ph += p.nph) {
+    const int nbp = min(p.nph, NB - ph);
+    if (ph > 0) __syncthreads();                   // every wave is done with the previous phase's rows
+    // ---- stage rows' chunks [ph * 256, (ph + nbp) * 256)
+    for (int c = tid; c < nbp * 256; c += 256) {
+      const int gc = ph * 256 + c;
+#pragma unroll
+      for (int r = 0; r < BR; ++r) {
+        u32x4_t v = ((const u32x4_t*)((const T*)p.x + (int64_t)min(r, p.B - 1) * p.ldx))[gc];
+        if (p.nw) {
+          float f[KPC];
+          dec_unpack<T>(v, f);
+          const f32x4_t* nw4 = (const f32x4_t*)p.nw + gc * NWV;
+#pragma unroll
+          for (int e = 0; e < KPC; ++e) f[e] = dec_round<T>(f[e] * rstd[r]) * nw4[e / 4][e % 4];
+          v = dec_pack<T>(f);
+        }
+        xs[r * pch + c] = v;
+      }
+    }
+    __syncthreads();
+    // ---- the stream: flat (pair, batch-of-phase) sequence, two batches in flight
+    const int total = np * nbp;
+    auto issue = [&](u32x4_t (&v0)[CPB], u32x4_t (&v1)[CPB], int it) {
+      const int pc = p0 + it / nbp, cb = ph + it % nbp;
+      const int n0 = RHD > 0 ? (pc / max(RHD, 1)) * (2 * RHD) + pc % max(RHD, 1) : GLU ? pc : 2 * pc;
+      const int n1 = RHD > 0 ? n0 + RHD : GLU ? p.N + pc : min(2 * pc + 1, p.N - 1);
+      const u32x4_t* w0 = (const u32x4_t*)(W + (int64_t)n0 * p.ldw) + cb * (64 * CPB) + lane;
+      const u32x4_t* w1 = (const u32x4_t*)(W + (int64_t)n1 * p.ldw) + cb * (64 * CPB) + lane;
+#pragma unroll
+      for (int u = 0; u < CPB; ++u) {
+        v0[u] = __builtin_nontemporal_load(w0 + u * 64);
+        v1[u] = __builtin_nontemporal_load(w1 + u * 64);
+      }
+    };
+    auto consume = [&](const u32x4_t (&v0)[CPB], const u32x4_t (&v1)[CPB], int it) {
+      const int li = it / nbp, cbl = it % nbp;
+#pragma unroll
+      for (int r = 0; r < BR; ++r) {               // row-outer keeps one row's x chunks live at a time; each row's sum order is the single-row one
+#pragma unroll
+        for (int u = 0; u < CPB; ++u) {
+          const u32x4_t xv = xs[r * pch + cbl * (64 * CPB) + u * 64 + lane];
+          a0[r] += dec_dot<T>(v0[u], xv);
+          a1[r] += dec_dot<T>(v1[u], xv);
+        }
+      }
+      if (cbl == nbp - 1 && ph + nbp == NB) {      // the pair's last batch
+#pragma unroll
+        for (int r = 0; r < BR; ++r) {
+          const float s0 = wave_sum(a0[r]), s1 = wave_sum(a1[r]);
+          if (lane == 0) { res[wave][li][r][0] = s0; res[wave][li][r][1] = s1; }
+          a0[r] = 0.f;
+          a1[r] = 0.f;
+        }
+      }
+    };
+    u32x4_t va0[CPB], va1[CPB], vb0[CPB], vb1[CPB];
+    if (total > 0) issue(va0, va1, 0);
+    if (total > 1) issue(vb0, vb1, 1);
+    int it = 0;
+    for (; it + 1 < total; it += 2) {
+      consume(va0, va1, it);
+      if (it + 2 < total) issue(va0, va1, it + 2);
+      consume(vb0, vb1, it + 1);
+      if (it + 3 < total) issue(vb0, vb1, it + 3);
+    }
+    if (it < total) consume(va0, va1, it);
+  }
+  // ---- epilogue: one lane per (pair, row); the single-row kernel's stores
+  for (int i = lane; i < np * BR; i += 64) {
+    const int li = i / BR, r = i % BR, pi = p0 + li;
+    if (r >= p.B) continue;
+    if constexpr (RHD > 0) {
+      const int pos = p.pos[r];
+      const int srow = min(max(pos - p.row0, 0), p.slot_rows - 1);    // a slot's rows only, whatever the position word holds
+      const int hh = pi / RHD, d = pi % RHD;
+      const float x1 = dec_round<TO>(res[wave][li][r][0]), x2 = dec_round<TO>(res[wave][li][r][1]);
+      float o1 = x1, o2 = x2;
+      TO* dst;
+      if (hh < p.H + p.Hkv) {
+        const float c = p.rope_cs[r * 2 * RHD + d], sv = p.rope_cs[r * 2 * RHD + RHD + d];
+        const float cb = bf2f(f2bf(c)), sb = bf2f(f2bf(sv));
+        o1 = bf2f(f2bf(x1 * cb)) + bf2f(f2bf(-x2 * sb));
+        o2 = bf2f(f2bf(x2 * cb)) + bf2f(f2bf(x1 * sb));
+        dst = hh < p.H ? (TO*)p.y + r * p.ldy + (int64_t)hh * (2 * RHD)
+                       : (TO*)p.kc + r * p.slot_stride + ((int64_t)srow * p.Hkv + (hh - p.H)) * (2 * RHD);
+      } else {
+        dst = (TO*)p.vc + r * p.slot_stride + ((int64_t)srow * p.Hkv + (hh - p.H - p.Hkv)) * (2 * RHD);
+      }
+      vg_elt<TO>::st(dst + d, o1);
+      vg_elt<TO>::st(dst + d + RHD, o2);
+    } else {
+      DecGemvArgs q{};
+      q.y = (TO*)p.y + r * p.ldy;
+      q.R = p.R ? (const void*)((const TO*)p.R + r * p.ldr) : nullptr;
+      q.N = p.N;
+      dec_gemv_store<T, TO, GLU>(q, pi, res[wave][li][r][0], res[wave][li][r][1]);
+    }
+  }
+}
+
+static int dec_rows_nb(int K) {
+  const int nch = K / 8;
+  if (K % 2048) return 0;
+  const int nb = nch / 256;
+  return nb == 1 || nb == 2 || nb == 4 || nb == 7 || nb == 8 ? nb : 0;
+}
+
+extern "C" int vg_decode_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype) {
+  return dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, hidden, dtype) && dec_rows_nb(hidden) && dec_rows_nb(inter) && (H * D) == hidden;
+}
+
+template <typename TO, bool GLU, int NB, int BR, int RHD>
+static int launch_rows_b(DecRowsArgs p, hipStream_t st) {
+  const int npair = RHD > 0 ? p.N / 2 : GLU ? p.N : (p.N + 1) / 2;
+  // x staging: the whole row when it fits the budget (always with the norm), else phases of batches with one pair per wave
+  int nph = NB;
+  if (!p.nw && (int64_t)BR * NB * 4096 > DEC_ROWS_LDS) nph = max(1, DEC_ROWS_LDS / (BR * 4096));
+  int ppw = (npair + 2047) / 2048;                  // ~2 workgroups per CU, as vg_decode_gemv
+  ppw = nph < NB ? 1 : min(ppw, DEC_ROWS_PPW);
+  p.nph = nph;
+  p.ppw = ppw;
+  const size_t lds = (size_t)BR * nph * 4096;
+  static size_t cap = 64 * 1024;
+  if (lds > 64 * 1024 && lds > cap) {
+    (void)hipFuncSetAttribute((const void*)decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    cap = lds;
+  }
+  decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+template <typename TO, bool GLU, int NB, int RHD>
+static int launch_rows_nb(DecRowsArgs p, hipStream_t st) {
+  if (p.B <= 1) return launch_rows_b<TO, GLU, NB, 1, RHD>(p, st);
+  if (p.B <= 2) return launch_rows_b<TO, GLU, NB, 2, RHD>(p, st);
+  if (p.B <= 4) return launch_rows_b<TO, GLU, NB, 4, RHD>(p, st);
+  if (p.B <= 8) return launch_rows_b<TO, GLU, NB, 8, RHD>(p, st);
+  return launch_rows_b<TO, GLU, NB, 16, RHD>(p, st);
+}
+
+template <bool GLU>
+static int launch_rows(DecRowsArgs p, hipStream_t st) {
+  switch (dec_rows_nb(p.K)) {
+    case 1: return launch_rows_nb<bf16_t, GLU, 1, 0>(p, st);
+    case 2: return launch_rows_nb<bf16_t, GLU, 2, 0>(p, st);
+    case 4: return launch_rows_nb<bf16_t, GLU, 4, 0>(p, st);
+    case 7: return launch_rows_nb<bf16_t, GLU, 7, 0>(p, st);
+    default: return launch_rows_nb<bf16_t, GLU, 8, 0>(p, st);
+  }
+}
+
+extern "C" int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
+                                   const void* R, int64_t ldr, int N, int K, int B, int glu, int dtype, vg_stream_t stream) {
+  VG_CHECK(x && W && y && N > 0 && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemv_rows: bad args N=%d B=%d", N, B);
+  VG_CHECK(dtype == VG_BF16 && dec_rows_nb(K), VG_ERR_UNSUPPORTED, "vg_decode_gemv_rows: bf16 rows of K = 2048 x {1, 2, 4, 7, 8} only (K=%d dtype=%d)", K, dtype);
+  VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)W) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
+           "vg_decode_gemv_rows: alignment (16 bytes; ldx / ldw multiples of 8)");
+  const int br = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;      // the bucket the kernel stages
+  VG_CHECK(!norm_w || (int64_t)br * K * 2 <= 160 * 1024 - 8 * 1024, VG_ERR_UNSUPPORTED,
+           "vg_decode_gemv_rows: the norm stages the whole rows of the %d-row bucket: B=%d K=%d do not fit", br, B, K);
+  DecRowsArgs p{x, ldx, W, ldw, y, ldy, norm_w, eps, R, ldr, N, K, B, 1, 1};
+  hipStream_t st = (hipStream_t)stream;
+  return glu ? launch_rows<true>(p, st) : launch_rows<false>(p, st);
+}
+
+extern "C" int vg_decode_qkv_rope_rows(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out,
+                                       int64_t ldq, void* k_slots, void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* rope_cs,
+                                       const int* pos, int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream) {
+  VG_CHECK(x && Wqkv && q_out && k_slots && v_slots && rope_cs && pos && B >= 1 && B <= 16 && slot_rows > 0, VG_ERR_ARG,
+           "vg_decode_qkv_rope_rows: bad args B=%d slot_rows=%d", B, slot_rows);
+  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
+           "vg_decode_qkv_rope_rows: H=%d Hkv=%d D=%d K=%d dtype=%d not covered", H, Hkv, D, K, dtype);
+  VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)Wqkv) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
+           "vg_decode_qkv_rope_rows: alignment (16 bytes; ldx / ldw multiples of 8)");
+  DecRowsArgs p{x, ldx, Wqkv, ldw, q_out, ldq, norm_w, eps, nullptr, 0, (H + 2 * Hkv) * D, K, B, 1, 1,
+                rope_cs, pos, k_slots, v_slots, slot_stride, row0, slot_rows, H, Hkv};
+  hipStream_t st = (hipStream_t)stream;
+  return K == 4096 ? launch_rows_nb<bf16_t, false, 2, 64>(p, st) : launch_rows_nb<bf16_t, false, 1, 64>(p, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Attention of the one new token.  grid = (ceil(max_len/64) splits, Hkv): a workgroup owns 64 keys of one KV head and
 // the G = H/Hkv query heads that share it.  All K and V bytes of the split are requested up front (one HBM round
 // trip), RoPE of q and of the new k runs while they are in flight, the workgroup that owns position `pos` appends the

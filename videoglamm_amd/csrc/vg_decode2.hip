@@ -40,11 +40,14 @@ struct DecAttn2Args {
   const bf16_t* q; const bf16_t* kc; const bf16_t* vc; bf16_t* o;
   float* ws; int* cnt; const int* pos_dev;
   int Hkv, max_len, nsplit, window; float scale; int64_t ws_bytes;
+  // ROWS form (vg_decode_attention2_rows): row b = blockIdx.z has its own query / output row, position pos_dev[b], counters and partials; key
+  // blocks from row0 (a multiple of the keys per workgroup) on come from slot b: ks / vs + b * slot_stride, rows [row0, row0 + slot_rows)
+  const bf16_t* ks; const bf16_t* vs; int64_t slot_stride; int row0, slot_rows;
 };
 
 constexpr int A2_D = 128, A2_PS = 132;      // partial row: 128 accumulators, max, sum, 2 pad (16-byte rows)
 
-template <int G, int NW>
+template <int G, int NW, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   extern __shared__ __attribute__((aligned(16))) char a2_smem[];
   __shared__ int ticket;
@@ -52,23 +55,33 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   float* red = (float*)a2_smem;              // [NW][4 r][G][128]
   float* ml = red + NW * 4 * G * A2_D;       // [NW][G][2]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane >> 4, c = lane & 15;
-  const int s = blockIdx.x, kvh = blockIdx.y;
+  const int s = blockIdx.x, b = ROWS ? (int)blockIdx.z : 0, kvh = blockIdx.y, hb = b * p.Hkv + kvh;     // hb: this (row, KV head)'s counter / partials
   const int j0 = s * KW + wave * 32;
 
   // ---- 1. every load up front; none of the addresses needs the position
   u32x4_t qv[G], kreg[8], vreg[8];
+  const bf16_t* qrow = p.q + (int64_t)b * p.Hkv * G * A2_D;
 #pragma unroll
-  for (int g = 0; g < G; ++g) qv[g] = *(const u32x4_t*)(p.q + (int64_t)(kvh * G + g) * A2_D + c * 8);
+  for (int g = 0; g < G; ++g) qv[g] = *(const u32x4_t*)(qrow + (int64_t)(kvh * G + g) * A2_D + c * 8);
   const int64_t rs = (int64_t)p.Hkv * A2_D;
   const bf16_t* kb = p.kc + (int64_t)kvh * A2_D + c * 8;
   const bf16_t* vb = p.vc + (int64_t)kvh * A2_D + c * 8;
+  int jb = j0, jlim = p.max_len;
+  if (ROWS && s * KW >= p.row0) {            // a per-slot key block
+    kb = p.ks + b * p.slot_stride + (int64_t)kvh * A2_D + c * 8;
+    vb = p.vs + b * p.slot_stride + (int64_t)kvh * A2_D + c * 8;
+    jb = j0 - p.row0;
+    jlim = p.slot_rows;
+  }
 #pragma unroll
-  for (int i = 0; i < 8; ++i) kreg[i] = *(const u32x4_t*)(kb + (int64_t)min(j0 + 4 * i + r, p.max_len - 1) * rs);
+  for (int i = 0; i < 8; ++i) kreg[i] = *(const u32x4_t*)(kb + (int64_t)min(jb + 4 * i + r, jlim - 1) * rs);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) vreg[i] = *(const u32x4_t*)(vb + (int64_t)min(j0 + 4 * i + r, p.max_len - 1) * rs);
-  const int pos = *p.pos_dev;
+  for (int i = 0; i < 8; ++i) vreg[i] = *(const u32x4_t*)(vb + (int64_t)min(jb + 4 * i + r, jlim - 1) * rs);
+  const int pos = p.pos_dev[b];
   const int lo = p.window > 0 ? max(0, pos + 1 - p.window) : 0;
-  const int active = pos / KW + 1, first = lo / KW;
+  // ROWS: a position past the grid's bound (the caller's n_bound) would leave splits that never arrive and the counter short of nact; the
+  // clamp keeps every launch's counters self-resetting (the rows past the bound are then not attended — RowsDecode refuses such a step on the host)
+  const int active = ROWS ? min(pos / KW + 1, p.nsplit) : pos / KW + 1, first = lo / KW;
   if (s >= active || s < first) return;
   const int nact = active - first;
 
@@ -130,7 +143,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   // ---- 4. the workgroup's partial: thread -> (head g, 4 columns); 16-byte WRITE-THROUGH (sc1) stores through a buffer descriptor, every
   //         storing wave drains, then ONE lane takes the ticket (MI355X_MICROARCH.md, valid hand-off forms; the reader uses sc1 loads)
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(p.ws, 0, (int)min(p.ws_bytes, (int64_t)0x7fffffff), 0x00020000);
-  const int pbase = (int)((((int64_t)kvh * p.nsplit + s) * G) * A2_PS * 4);
+  const int pbase = (int)((((int64_t)hb * p.nsplit + s) * G) * A2_PS * 4);
   if (tid < G * 32) {
     const int g = tid >> 5, d4 = tid & 31;
     float M = -INFINITY;
@@ -157,7 +170,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (tid == 0) ticket = __hip_atomic_fetch_add(&p.cnt[kvh], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) ticket = __hip_atomic_fetch_add(&p.cnt[hb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   if (ticket != nact - 1) return;
   // ---- 5. merge by the last workgroup of this KV head to arrive.  ALL its threads load: thread group q (128 threads = one (head, 4 columns) map)
@@ -168,7 +181,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
     constexpr int NG = NW * 64 / GS;
     const int grp = tid / GS, t7 = tid % GS, g = (t7 >> 5) % G, d4 = t7 & 31;
     const bool live = t7 < G * 32;
-    const int mbase = (int)((((int64_t)kvh * p.nsplit + first) * G) * A2_PS * 4);
+    const int mbase = (int)((((int64_t)hb * p.nsplit + first) * G) * A2_PS * 4);
     float M = -INFINITY, L = 0.f;
     f32x4_t o = {0.f, 0.f, 0.f, 0.f};
     for (int b0 = 0; b0 < nact; b0 += 8 * NG) {
@@ -218,21 +231,21 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
       }
       const float inv = 1.0f / Lt;
       uint2 ov = {f2bf2(ot[0] * inv, ot[1] * inv), f2bf2(ot[2] * inv, ot[3] * inv)};
-      *(uint2*)(p.o + (int64_t)(kvh * G + g) * A2_D + d4 * 4) = ov;
+      *(uint2*)(p.o + (int64_t)b * p.Hkv * G * A2_D + (int64_t)(kvh * G + g) * A2_D + d4 * 4) = ov;
     }
   }
-  if (tid == 0) __hip_atomic_store(&p.cnt[kvh], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __hip_atomic_store(&p.cnt[hb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int G, int NW>
-static int launch_attn2(const DecAttn2Args& p, hipStream_t st) {
+template <int G, int NW, bool ROWS = false>
+static int launch_attn2(const DecAttn2Args& p, hipStream_t st, int B = 1) {
   const size_t lds = sizeof(float) * ((size_t)NW * 4 * G * A2_D + NW * G * 2);
   static size_t cap = 64 * 1024;
   if (lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_attn2_kernel<G, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)decode_attn2_kernel<G, NW, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     cap = lds;
   }
-  decode_attn2_kernel<G, NW><<<dim3(p.nsplit, p.Hkv), NW * 64, lds, st>>>(p);
+  decode_attn2_kernel<G, NW, ROWS><<<dim3(p.nsplit, p.Hkv, B), NW * 64, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
@@ -267,6 +280,45 @@ extern "C" int vg_decode_attention2(const void* q, const void* k_cache, const vo
     default: VG_A2(8);
   }
 #undef VG_A2
+}
+
+// B query rows at once (the batched multi-prompt decode step): grid z = row.  Row b is decode_attn2_kernel's row b alone — the same
+// 32-key wave groups, the same LDS merge of the NW waves, the same split-order merge of its own partials — so it is bit-identical to
+// vg_decode_attention2 on that row with the whole cache in one array.  Key blocks below row0 are shared by every row (the prefix, k_cache /
+// v_cache); blocks from row0 on are slot b's (k_slots / v_slots + b * slot_stride, row j at j - row0).  n_bound: a host-known bound on every
+// position + 1 over the launches the caller replays (the grid covers ceil(n_bound / keys_per_wg) splits, not the cache length).
+extern "C" int64_t vg_decode_attention2_rows_ws_floats(int H, int Hkv, int D, int n_bound, int keys_per_wg, int B) {
+  if (H <= 0 || Hkv <= 0 || D <= 0 || n_bound <= 0 || B <= 0 || (keys_per_wg != 128 && keys_per_wg != 256)) return -1;
+  const int nsplit = (n_bound + keys_per_wg - 1) / keys_per_wg;
+  return (int64_t)B * Hkv * nsplit * (H / Hkv) * A2_PS + (int64_t)B * Hkv;
+}
+
+extern "C" int vg_decode_attention2_rows(const void* q, const void* k_cache, const void* v_cache, int max_len, const void* k_slots, const void* v_slots,
+                                         int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D, int n_bound, int window, float scale,
+                                         const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg, int B, int dtype, vg_stream_t stream) {
+  VG_CHECK(q && k_cache && v_cache && k_slots && v_slots && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_attention2_rows: bad args");
+  VG_CHECK(vg_decode_attention2_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "vg_decode_attention2_rows: H=%d Hkv=%d D=%d dtype=%d not covered", H, Hkv, D, dtype);
+  VG_CHECK(keys_per_wg == 128 || keys_per_wg == 256, VG_ERR_ARG, "vg_decode_attention2_rows: keys_per_wg %d not in {128, 256}", keys_per_wg);
+  VG_CHECK(row0 >= 0 && row0 % keys_per_wg == 0 && row0 <= max_len && slot_rows > 0 && n_bound > row0 && n_bound <= row0 + slot_rows && window >= 0, VG_ERR_ARG,
+           "vg_decode_attention2_rows: row0=%d (a multiple of %d, <= max_len %d), slot_rows=%d, n_bound=%d in (row0, row0 + slot_rows]", row0, keys_per_wg, max_len,
+           slot_rows, n_bound);
+  VG_CHECK((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k_slots | (uintptr_t)v_slots | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 &&
+               slot_stride % 8 == 0, VG_ERR_ARG, "vg_decode_attention2_rows: 16-byte alignment");
+  const int64_t need = vg_decode_attention2_rows_ws_floats(H, Hkv, D, n_bound, keys_per_wg, B);
+  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention2_rows: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
+  const int G = H / Hkv;
+  const int nsplit = (n_bound + keys_per_wg - 1) / keys_per_wg;
+  DecAttn2Args p{(const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_cache, (bf16_t*)out, workspace, (int*)(workspace + (ws_floats - (int64_t)B * Hkv)), pos,
+                 Hkv, max_len, nsplit, window, scale, ws_floats * 4, (const bf16_t*)k_slots, (const bf16_t*)v_slots, slot_stride, row0, slot_rows};
+  hipStream_t st = (hipStream_t)stream;
+#define VG_A2R(GG) return keys_per_wg == 256 ? launch_attn2<GG, 8, true>(p, st, B) : launch_attn2<GG, 4, true>(p, st, B)
+  switch (G) {
+    case 1: VG_A2R(1);
+    case 2: VG_A2R(2);
+    case 4: VG_A2R(4);
+    default: VG_A2R(8);
+  }
+#undef VG_A2R
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -360,6 +412,73 @@ extern "C" int vg_decode_step_end(uint64_t* acc, int64_t* tok, int* pos, int* st
   const int es = dtype == VG_BF16 ? 2 : 4;
   VG_CHECK((D * es) % 16 == 0 && (((uintptr_t)row | (uintptr_t)hid_all) & 15) == 0, VG_ERR_ARG, "vg_decode_step_end: rows must be whole 16-byte chunks, 16-byte aligned");
   decode_step_end_kernel<<<1, 256, 0, (hipStream_t)stream>>>((unsigned long long*)acc, tok, pos, step, forced, n_forced, hist, raw, cap, row, hid_all, D, es);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+// B-row forms of the step's head and tail (the batched multi-prompt decode step): row b = blockIdx.y (begin) / blockIdx.x (end) does exactly what
+// the single-row kernel does for its own token, position, step counter, accumulator, history, forcing table and final-norm rows.
+//   begin: x[b] = table[tok[b]], rope_cs[b] = [cos[pos[b]] | sin[pos[b]]]
+//   end:   tok[b] = index from acc[b] (acc[b] = 0 again); hid[b][pos[b] - hid_row0] = row b (hid + b * hid_stride, rows clamped to [0, hid_rows)); then the bookkeeping
+//          on forced / hist / raw + b * cap; pos[b] += 1
+__global__ __launch_bounds__(256) void decode_step_begin_rows_kernel(const int64_t* tok, const void* table, void* x, int D, int es, const int* pos,
+                                                                     const float* cosT, const float* sinT, float* rope_cs, int hd) {
+  const int b = blockIdx.y;
+  const int64_t t = tok[b];
+  const int nb = D * es / 16;
+  const u32x4_t* src = (const u32x4_t*)((const char*)table + t * (int64_t)D * es);
+  u32x4_t* dst = (u32x4_t*)((char*)x + (int64_t)b * D * es);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nb; i += gridDim.x * 256) dst[i] = src[i];
+  if (blockIdx.x == 0 && rope_cs) {
+    const int np = pos[b];
+    for (int d = threadIdx.x; d < 2 * hd; d += 256) rope_cs[b * 2 * hd + d] = d < hd ? cosT[(int64_t)np * hd + d] : sinT[(int64_t)np * hd + d - hd];
+  }
+}
+
+extern "C" int vg_decode_step_begin_rows(const int64_t* tok, const void* table, void* x, int D, int dtype, const int* pos, const float* cos, const float* sin,
+                                         float* rope_cs, int half_dim, int B, vg_stream_t stream) {
+  VG_CHECK(tok && table && x && pos && D > 0 && B >= 1 && (dtype == VG_BF16 || dtype == VG_F32), VG_ERR_ARG, "vg_decode_step_begin_rows: bad args");
+  const int es = dtype == VG_BF16 ? 2 : 4;
+  VG_CHECK((D * es) % 16 == 0 && (((uintptr_t)table | (uintptr_t)x) & 15) == 0, VG_ERR_ARG, "vg_decode_step_begin_rows: rows must be whole 16-byte chunks, 16-byte aligned");
+  VG_CHECK(!rope_cs || (cos && sin && half_dim > 0), VG_ERR_ARG, "vg_decode_step_begin_rows: rope_cs needs the cos / sin tables");
+  decode_step_begin_rows_kernel<<<dim3((D * es / 16 + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(tok, table, x, D, es, pos, cos, sin, rope_cs, half_dim);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+__global__ __launch_bounds__(256) void decode_step_end_rows_kernel(unsigned long long* acc, int64_t* tok, int* pos, int* step, const int64_t* forced, int n_forced,
+                                                                   int64_t* hist, int64_t* raw, int cap, const void* row, void* hid, int64_t hid_stride, int hid_row0,
+                                                                   int hid_rows, int D, int es) {
+  const int b = blockIdx.x;
+  const int p0 = pos[b];
+  const int nb = D * es / 16;
+  const u32x4_t* src = (const u32x4_t*)((const char*)row + (int64_t)b * D * es);
+  u32x4_t* dst = (u32x4_t*)((char*)hid + ((int64_t)b * hid_stride + (int64_t)min(max(p0 - hid_row0, 0), hid_rows - 1) * D) * es);
+  for (int i = threadIdx.x; i < nb; i += 256) dst[i] = src[i];
+  if (threadIdx.x == 0) {
+    const int k = step[b];
+    const int64_t t0 = (int64_t)(0xffffffffu - (uint32_t)(acc[b] & 0xffffffffull));
+    acc[b] = 0;
+    int64_t t = t0;
+    if (forced && k < n_forced && forced[(int64_t)b * n_forced + k] >= 0) t = forced[(int64_t)b * n_forced + k];
+    if (raw && k < cap) raw[(int64_t)b * cap + k] = t0;
+    if (hist && k < cap) hist[(int64_t)b * cap + k] = t;
+    tok[b] = t;
+    step[b] = k + 1;
+    pos[b] = p0 + 1;
+  }
+}
+
+extern "C" int vg_decode_step_end_rows(uint64_t* acc, int64_t* tok, int* pos, int* step, const int64_t* forced, int n_forced, int64_t* hist, int64_t* raw,
+                                       int cap, const void* row, void* hid, int64_t hid_stride, int hid_row0, int hid_rows, int D, int dtype, int B,
+                                       vg_stream_t stream) {
+  VG_CHECK(acc && tok && pos && step && row && hid && D > 0 && B >= 1 && hid_rows > 0 && (dtype == VG_BF16 || dtype == VG_F32), VG_ERR_ARG,
+           "vg_decode_step_end_rows: bad args");
+  const int es = dtype == VG_BF16 ? 2 : 4;
+  VG_CHECK((D * es) % 16 == 0 && (((uintptr_t)row | (uintptr_t)hid) & 15) == 0 && hid_stride % 8 == 0 && hid_stride >= (int64_t)hid_rows * D, VG_ERR_ARG,
+           "vg_decode_step_end_rows: rows must be whole 16-byte chunks, 16-byte aligned; slots must not overlap");
+  decode_step_end_rows_kernel<<<B, 256, 0, (hipStream_t)stream>>>((unsigned long long*)acc, tok, pos, step, forced, n_forced, hist, raw, cap, row, hid,
+                                                                   hid_stride, hid_row0, hid_rows, D, es);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }

@@ -803,6 +803,103 @@ def decode_step_end(acc, tok_dev, pos_dev, step_dev, row, hid_all, forced=None, 
     _lib.check(rc, "vg_decode_step_end")
 
 
+# ---- the batched multi-prompt decode step: B <= 16 rows, row b bit-identical to the single-row kernel on that row alone
+def decode_rows_supported(H, Hkv, D, hidden, inter, dtype):
+    """True when the B-row decode kernels cover a bf16 Llama layer of this shape (vg_decode_rows_supported)."""
+    return dtype == torch.bfloat16 and bool(_lib.load().vg_decode_rows_supported(H, Hkv, D, hidden, inter, BF16))
+
+
+def decode_gemv_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out=None):
+    """decode_gemv on each of the B rows of x [B,K] (vg_decode_gemv_rows): one pass over w for all rows -> [B,N]."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and x.dtype == torch.bfloat16
+    N = w.shape[0] // 2 if glu else w.shape[0]
+    y = out if out is not None else torch.empty(B, N, dtype=x.dtype, device=x.device)
+    assert y.shape == (B, N) and y.stride(1) == 1
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
+        ldr = residual.stride(0)
+    rc = lib.vg_decode_gemv_rows(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)), float(eps),
+                                 _p(residual), ldr, N, K, B, int(bool(glu)), _dt(x), _stream())
+    _lib.check(rc, "vg_decode_gemv_rows")
+    return y
+
+
+def decode_qkv_rope_rows(x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out=None):
+    """decode_qkv_rope on each row of x [B,K]: row b at position pos_dev[b] with rope_cs[b], its K / V rows into slot b of k_slots / v_slots
+    ([B, rows, Hkv, D], row j of the sequence at j - row0) -> rotated q [B, H*D]."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and wqkv.stride(1) == 1 and wqkv.shape == ((H + 2 * Hkv) * D, K) and pos_dev.dtype == torch.int32 and pos_dev.numel() >= B
+    assert k_slots.is_contiguous() and v_slots.is_contiguous() and k_slots.shape[0] >= B and k_slots.shape[2:] == (Hkv, D) and k_slots.shape == v_slots.shape
+    assert rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and rope_cs.shape[-1] == D and rope_cs.shape[0] >= B
+    q = out if out is not None else torch.empty(B, H * D, dtype=x.dtype, device=x.device)
+    rc = lib.vg_decode_qkv_rope_rows(_p(x), x.stride(0), _p(wqkv), wqkv.stride(0), _p(_f32(norm_w)), float(eps), _p(q), q.stride(0), _p(k_slots), _p(v_slots),
+                                     k_slots.stride(0), int(row0), k_slots.shape[1], _p(rope_cs), _p(pos_dev), H, Hkv, D, K, B, _dt(x), _stream())
+    _lib.check(rc, "vg_decode_qkv_rope_rows")
+    return q
+
+
+def decode_attention2_rows_workspace(H, Hkv, D, n_bound, keys_per_wg, B, device):
+    n = _lib.load().vg_decode_attention2_rows_ws_floats(H, Hkv, D, int(n_bound), int(keys_per_wg), int(B))
+    if n < 0:
+        raise _lib.VGKernelError(f"vg_decode_attention2_rows_ws_floats: bad shape H={H} Hkv={Hkv} D={D} n_bound={n_bound} B={B}")
+    return torch.zeros(n, dtype=torch.float32, device=device)
+
+
+def decode_attention2_rows(q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, D, pos_dev, n_bound, scale, ws, window=0, keys_per_wg=256):
+    """decode_attention2 on each row of q [B, H*D]: keys [0, row0) from the shared caches, [row0, pos_dev[b]] from slot b -> [B, H*D]."""
+    lib = _lib.load()
+    B = q.shape[0]
+    assert q.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous() and k_slots.is_contiguous() and v_slots.is_contiguous()
+    assert pos_dev.dtype == torch.int32 and k_slots.shape[0] >= B
+    out = torch.empty(B, H * D, dtype=q.dtype, device=q.device)
+    rc = lib.vg_decode_attention2_rows(_p(q), _p(k_cache), _p(v_cache), k_cache.shape[0], _p(k_slots), _p(v_slots), k_slots.stride(0), int(row0), k_slots.shape[1],
+                                       _p(out), H, Hkv, D, int(n_bound), int(window), float(scale), _p(pos_dev), _p(ws), ws.numel(), int(keys_per_wg), B, _dt(q),
+                                       _stream())
+    _lib.check(rc, "vg_decode_attention2_rows")
+    return out
+
+
+def decode_step_begin_rows(tok_dev, table, pos_dev, rope=None):
+    """decode_step_begin per row: x[b] = table[tok_dev[b]] -> [B, D]; rope = (cos, sin, rope_cs [B, 2*half]): rope_cs[b] = cos / sin rows of pos_dev[b]."""
+    lib = _lib.load()
+    B = tok_dev.numel()
+    assert tok_dev.dtype == torch.int64 and table.is_contiguous() and pos_dev.dtype == torch.int32 and pos_dev.numel() >= B
+    D = table.shape[1]
+    x = torch.empty(B, D, dtype=table.dtype, device=table.device)
+    cos, sin, rope_cs = rope if rope is not None else (None, None, None)
+    if rope is not None:
+        assert rope_cs.is_contiguous() and rope_cs.shape[0] >= B and rope_cs.shape[-1] == 2 * cos.shape[1]
+    rc = lib.vg_decode_step_begin_rows(_p(tok_dev), _p(table), _p(x), D, _dt(table), _p(pos_dev), _p(cos), _p(sin), _p(rope_cs),
+                                       0 if rope is None else cos.shape[1], B, _stream())
+    _lib.check(rc, "vg_decode_step_begin_rows")
+    return x
+
+
+def decode_step_end_rows(acc, tok_dev, pos_dev, step_dev, rows, hid, forced=None, hist=None, raw=None, hid_row0=0):
+    """decode_step_end per row b: acc / tok / pos / step [b], final-norm row rows[b] into hid[b][pos[b] - hid_row0] (hid [B, n, D]), forced / hist / raw [B, cap]."""
+    lib = _lib.load()
+    B, D = rows.shape
+    assert rows.is_contiguous() and hid.is_contiguous() and hid.dim() == 3 and hid.shape[0] >= B and hid.shape[2] == D and rows.dtype == hid.dtype
+    assert all(t.numel() >= B for t in (acc, tok_dev, pos_dev, step_dev))
+    cap = 0 if hist is None else hist.shape[1]
+    assert all(t is None or (t.is_contiguous() and t.shape[0] >= B) for t in (forced, hist, raw)) and (raw is None or raw.shape[1] == cap)
+    rc = lib.vg_decode_step_end_rows(_p(acc), _p(tok_dev), _p(pos_dev), _p(step_dev), _p(forced), 0 if forced is None else forced.shape[1], _p(hist), _p(raw),
+                                     cap, _p(rows), _p(hid), hid.stride(0), int(hid_row0), hid.shape[1], D, _dt(rows), B, _stream())
+    _lib.check(rc, "vg_decode_step_end_rows")
+
+
+def argmax_partial_rows(x, acc):
+    """argmax_partial of each row of x [B, n] into acc[b] (one launch; vg_argmax_partial)."""
+    lib = _lib.load()
+    x = x.contiguous()
+    assert acc.dtype == torch.int64 and acc.numel() >= x.shape[0]
+    _lib.check(lib.vg_argmax_partial(_p(x), x.shape[0], x.shape[1], _p(acc), _dt(x), _stream()), "vg_argmax_partial")
+
+
 def decode_layer_roles(H, Hkv, D, hidden, inter, dtype):
     """0 / 1 / 3: which roles vg_decode_layer covers for this shape (0: use decode_attention + decode_gemv)."""
     return int(_lib.load().vg_decode_layer_roles(H, Hkv, D, hidden, inter, F32 if dtype == torch.float32 else BF16))

@@ -7,12 +7,47 @@ several questions about one clip (R/eval_referdavis_infer.py:143-205, R/eval_mev
 The prefix is a property of each prompt, never of the batch (no common-prefix search): a prompt's prefill splits at the same row
 whatever it is batched with, so its arithmetic does not depend on the other prompts.
 """
+import os
+
 import torch
 
 from . import ops
-from .vlm import IMAGE_TOKEN_INDEX, LlamaDecoder, decode_loop, splice, stage_mark
+from .vlm import IMAGE_TOKEN_INDEX, LlamaDecoder, RowsDecode, decode_loop, splice, stage_mark
 
 GROUP = 16       # prompts per pass; longer lists run in consecutive groups
+BUCKETS = (2, 4, 8, 16)     # rows of a captured batched decode step
+
+
+def bucket(B):
+    """the captured batched step that runs B prompts: the smallest bucket >= B"""
+    for n in BUCKETS:
+        if B <= n:
+            return n
+    raise ValueError(f"{B} prompts: a batched decode step runs at most {BUCKETS[-1]}")
+
+
+def sampling_route(sampling, vocab):
+    """"greedy", "sample_fast" or "sample": the launches a prompt's decode step captures (LlamaDecoder.set_sampling)"""
+    if sampling is None:
+        return "greedy"
+    return "sample_fast" if ops.sample_fast_route(int(sampling["k"]), vocab) else "sample"
+
+
+def batched_route(B, rope_path, decode_weights, chain, routes, env):
+    """True when a group of B prompts decodes in one batched step (RowsDecode) instead of one after another.  rope_path: the decoder runs the
+    bf16 head_dim-128 rope step (LlamaDecoder.rope_path; B-row kernels cover the shape); decode_weights: cfg["decode_weights"]; chain: VG_DECODE_CHAIN
+    roles; routes: the set of the prompts' sampling routes; env: the environment (VG_PROMPTS_BATCHED=0 forces the sequential loop; VG_DECODE_AHEAD=1
+    keeps it too).  Pure: no device work."""
+    return (B >= 2 and B <= BUCKETS[-1] and bool(rope_path) and decode_weights != "fp8" and not chain and len(set(routes)) == 1
+            and env.get("VG_PROMPTS_BATCHED", "1") != "0" and env.get("VG_DECODE_AHEAD", "0") != "1")
+
+
+def slot_layout(P, kw, need):
+    """(row0, n_bound): slot rows start at the key block that holds position P (row0 = floor(P / kw) * kw, so a key block is wholly shared or
+    wholly per slot) and end at `need` (every position a prompt of the group reaches is < need)"""
+    row0 = (P // kw) * kw
+    assert need > P >= row0
+    return row0, need
 
 
 def prefix_len(input_ids, b=0):
@@ -65,7 +100,35 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
     stage_mark(stages, "prefill")
     if after_prefix is not None:
         after_prefix()
+    vocab = params.t("lm_head.weight").shape[0]
+    routes = [sampling_route(sp, vocab) for sp in samplings]
+    batched = max_new_tokens > 1 and batched_route(B, dec.rope_path and ops.decode_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype),
+                                                   cfg["llm"].get("decode_weights"), dec.chain_roles, routes, os.environ)
+    rows = None
+    if batched:
+        row0, n_bound = slot_layout(P, dec.kpw2, need)
+        key = (bucket(B), row0, n_bound)
+        rows = dec.__dict__.setdefault("_rows", {}).get(key)
+        if rows is None:
+            dec._rows.clear()          # one batched state per decoder: its slots are sized by the clip
+            rows = dec._rows[key] = RowsDecode(dec, bucket(B), row0, n_bound)
+        rows.route = routes[0]
     out, embs, counts = [], [], []
+    added = P - n0                     # "num_newly_added_tokens" (VideoGLaMM.py:613,786)
+
+    def take(b, out_b):
+        # the row of a [SEG] at output position j is j - 1 + added (generate()); rows >= P belong to prompt b: the sequential loop takes them
+        # before the next prompt overwrites them, the batched one reads them from slot b
+        seg_rows = [j - 1 + added for j in range(1, len(out_b)) if out_b[j] == seg_idx]
+        if seg_rows:
+            # text_hidden_fcs per prompt: the GEMMs then see the same rows whether the prompt runs alone or in a batch
+            h = rows.rows_of(b, P, seg_rows) if rows is not None else dec.hid_all[torch.tensor(seg_rows, device=params.device)]
+            fc = "model.text_hidden_fcs.0."
+            h = ops.linear(h, params.w(fc + "0"), params.b(fc + "0"), act=ops.ACT_RELU)
+            embs.append(ops.linear(h, params.w(fc + "2"), params.b(fc + "2")))
+        counts.append(len(seg_rows))
+        return torch.tensor(out_b, dtype=torch.int64)
+
     for b, ids in enumerate(ids_list):
         dec.reset()
         dec.pos = P
@@ -76,19 +139,53 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
         out_b = ids.tolist()
         if max_new_tokens > 0:
             dec.next_token(hidden)
+        if rows is not None:
+            rows.load_row(b, P, P + ids.numel() - n0)      # the decode waits for the whole group
+            out.append(out_b)
+            continue
         decode_loop(params, dec, out_b, max_new_tokens, eos, token_hook, None if traces is None else traces[b])
-        added = P - n0                 # "num_newly_added_tokens" (VideoGLaMM.py:613,786)
-        # the row of a [SEG] at output position j is j - 1 + added (generate()); rows >= P belong to this prompt and are taken now
-        rows = [j - 1 + added for j in range(1, len(out_b)) if out_b[j] == seg_idx]
-        if rows:
-            # text_hidden_fcs per prompt: the GEMMs then see the same rows whether the prompt runs alone or in a batch
-            h = dec.hid_all[torch.tensor(rows, device=params.device)]
-            fc = "model.text_hidden_fcs.0."
-            h = ops.linear(h, params.w(fc + "0"), params.b(fc + "0"), act=ops.ACT_RELU)
-            embs.append(ops.linear(h, params.w(fc + "2"), params.b(fc + "2")))
-        counts.append(len(rows))
-        out.append(torch.tensor(out_b, dtype=torch.int64))
+        out.append(take(b, out_b))
+    if rows is not None:
+        for b in range(B, rows.B):
+            rows.pad_row(b, P)
+        decode_rows(rows, out, max_new_tokens, eos, token_hook, traces)
+        out = [take(b, out_b) for b, out_b in enumerate(out)]
     stage_mark(stages, "decode")
     if not embs:
         return out, torch.empty(0, 256, dtype=params.dtype, device=params.device), counts
     return out, torch.cat(embs), counts
+
+
+def _ffn(params):
+    return params.t("model.layers.0.mlp.down_proj.weight").shape[1]
+
+
+def decode_rows(rows, out, max_new_tokens, eos, token_hook=None, traces=None):
+    """decode_loop for the live rows of a batched step: per step the B tokens come back in one copy; each prompt applies token_hook with its own step
+    numbering (all prompts start together, so that is the loop's step), records trace["argmax"], appends, and retires at an id of `eos` or at
+    max_new_tokens; replaced tokens go back in one copy; the step is replayed while any prompt is live."""
+    B = len(out)
+    live = [True] * B
+    for step in range(max_new_tokens):
+        toks = rows.tok.cpu().tolist()
+        repl_any = False
+        for b in range(B):
+            if not live[b]:
+                continue
+            nxt = int(toks[b])
+            if traces is not None and traces[b] is not None:
+                traces[b].setdefault("argmax", []).append(nxt)
+            if token_hook is not None:
+                repl = token_hook(step, nxt)
+                if repl is not None and int(repl) != nxt:
+                    nxt = int(repl)
+                    toks[b] = nxt
+                    repl_any = True
+            out[b].append(nxt)
+            if nxt in eos or step == max_new_tokens - 1:
+                live[b] = False
+        if not any(live):
+            break
+        if repl_any:
+            rows.tok.copy_(torch.tensor(toks, dtype=torch.int64))
+        rows.decode_step()

@@ -488,6 +488,129 @@ class LlamaDecoder:
         self.pos += 1
 
 
+class RowsDecode:
+    """The batched decode step of several prompts that share the prefix rows [0, P) of a LlamaDecoder (prompts.generate_prompts): one
+    step consumes one token per row and emits one token per row; row b is bit-identical to the single-row step of prompt b alone.
+
+    Key / value rows below row0 = floor(P / kw) * kw (kw = the attention's keys per workgroup) are read from the decoder's caches; every row b has its
+    own zero-filled slot of rows [row0, n_bound) (the straddling block [row0, P) copied in once, then its suffix prefill and its decode rows), its
+    own final-norm rows (hid[b], position p at p - row0), token, position, step counter, accumulator, forcing table and sampling parameter block.
+    The step is captured once per sampling route ("greedy" / "sample_fast" / "sample") into a HIP graph; a new seed or temperature is a copy into
+    samp_params.  Rows past the live prompts (bucket padding) and retired rows keep computing into their own slots; their tokens are ignored."""
+
+    def __init__(self, dec, bucket, row0, n_bound):
+        self.dec, self.B, self.row0, self.n_bound = dec, bucket, row0, n_bound
+        d, dev, dt = dec, dec.P.device, dec.P.dtype
+        B = bucket
+        rows = n_bound - row0
+        self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
+        self.vs = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
+        self.hid = torch.zeros(B, rows, d.D, dtype=dt, device=dev)
+        self.tok = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.step = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.acc = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.hist = torch.zeros(B, d.HIST, dtype=torch.int64, device=dev)
+        self.raw = torch.zeros(B, d.HIST, dtype=torch.int64, device=dev)
+        self.forced = torch.full((B, d.HIST), -1, dtype=torch.int64, device=dev)
+        self.rope_cs = torch.zeros(B, d.hd, dtype=torch.float32, device=dev)
+        self.samp_params = torch.zeros(B, 6, dtype=torch.int32, device=dev)
+        self.samp_ws = None
+        self.attn_ws = ops.decode_attention2_rows_workspace(d.H, d.Hkv, d.hd, n_bound, d.kpw2, B, dev)
+        self.route = "greedy"
+        self.graphs = {}
+        self.steps = 0          # replayed (or eager) steps since the object was made: the batched loop's step count
+        self.host_pos = [0] * B  # every row's position, known on the host: a step past n_bound is refused before it is launched
+        self.start_pos = [0] * B  # the positions the rows were loaded at (load_row / pad_row)
+
+    def load_row(self, b, P, end):
+        """row b continues from the decoder's state after prompt b's suffix prefill and first token: its K / V rows [row0, end) and final-norm rows
+        [P, end) are copied into slot b; token, position (end), step (1: the prefill's token is step 0) and sampling block from the decoder."""
+        d = self.dec
+        for i in range(d.c["num_layers"]):
+            self.ks[i][b, :end - self.row0].copy_(d.kc[i][self.row0:end])
+            self.vs[i][b, :end - self.row0].copy_(d.vc[i][self.row0:end])
+        self.hid[b, P - self.row0:end - self.row0].copy_(d.hid_all[P:end])
+        self.host_pos[b] = self.start_pos[b] = end
+        self.tok[b:b + 1].copy_(d.tok_dev)
+        self.pos[b] = end
+        self.step[b] = 1
+        self.acc[b] = 0
+        self.forced[b].fill_(-1)
+        if d.sampling is not None:
+            self.samp_params[b].copy_(d.samp_params)
+
+    def pad_row(self, b, P, like=0):
+        """a bucket row without a prompt: position P of its own slot, token 0, row `like`'s sampling block"""
+        self.tok[b] = 0
+        self.pos[b] = P
+        self.host_pos[b] = self.start_pos[b] = P
+        self.step[b] = 1
+        self.acc[b] = 0
+        self.samp_params[b].copy_(self.samp_params[like])
+
+    def _step(self):
+        d, P, c = self.dec, self.dec.P, self.dec.c
+        x = ops.decode_step_begin_rows(self.tok, P.t("model.embed_tokens.weight"), self.pos, rope=(d.cos, d.sin, self.rope_cs))
+        for i in range(c["num_layers"]):
+            l = f"model.layers.{i}."
+            wqkv, _ = P.fused([l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"], stored=l + "self_attn.qkv_proj")
+            q = ops.decode_qkv_rope_rows(x, wqkv, P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i], self.row0, self.rope_cs,
+                                         self.pos, d.H, d.Hkv, d.hd)
+            o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
+                                           d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
+            x = ops.decode_gemv_rows(o, P.w(l + "self_attn.o_proj"), residual=x)
+            wgu, _ = P.fused([l + "mlp.gate_proj", l + "mlp.up_proj"], stored=l + "mlp.gate_up_proj")
+            a = ops.decode_gemv_rows(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
+            x = ops.decode_gemv_rows(a, P.w(l + "mlp.down_proj"), residual=x)
+        h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
+        logits = ops.linear(h, P.w("lm_head"), out_dtype=torch.float32)
+        if self.route == "greedy":
+            ops.argmax_partial_rows(logits, self.acc)
+        else:
+            for b in range(self.B):     # vg_sample per row: its own parameter block, step counter and accumulator
+                ops.sample_partial(logits[b], self.samp_params[b], self.step[b:b + 1], acc=self.acc[b:b + 1],
+                                   fast_ws=self.samp_ws if self.route == "sample_fast" else None)
+        ops.decode_step_end_rows(self.acc, self.tok, self.pos, self.step, h, self.hid, forced=self.forced, hist=self.hist, raw=self.raw,
+                                 hid_row0=self.row0)
+
+    def set_positions(self, pos):
+        """rows' positions (host list, each in [row0, n_bound)): written to the device and tracked on the host"""
+        assert all(self.row0 <= p < self.n_bound for p in pos)
+        self.host_pos = list(pos)
+        self.pos.copy_(torch.tensor(pos, dtype=torch.int32))
+
+    def decode_step(self):
+        if max(self.host_pos) >= self.n_bound:
+            raise ValueError(f"RowsDecode: a row at position {max(self.host_pos)} is past the slots' bound {self.n_bound}")
+        if self.route != "greedy" and self.samp_ws is None:
+            self.samp_ws = ops.sample_workspace(self.dec.P.device)
+        self.steps += 1
+        self.host_pos = [p + 1 for p in self.host_pos]
+        if not self.dec.use_graph:
+            self._step()
+            return
+        g = self.graphs.get(self.route)
+        if g is None:
+            # one eager step first (lazy weight packing, kernel attributes), then rewind and capture — as LlamaDecoder.decode_step
+            snap = [t.clone() for t in (self.tok, self.pos, self.step)]
+            self._step()
+            torch.cuda.synchronize()
+            for t, v in zip((self.tok, self.pos, self.step), snap):
+                t.copy_(v)
+            g = torch.cuda.CUDAGraph()
+            with ops.graph_capture(g):
+                self._step()
+            self.graphs[self.route] = g
+            for t, v in zip((self.tok, self.pos, self.step), snap):
+                t.copy_(v)
+        g.replay()
+
+    def rows_of(self, b, P, rows):
+        """final-norm rows of prompt b at sequence rows `rows`: below P from the decoder (the shared prefix), from P on from slot b"""
+        d = self.dec
+        return torch.stack([d.hid_all[r] if r < P else self.hid[b, r - self.row0] for r in rows])
+
 def splice(params, input_ids, visual):
     """prepare_inputs_labels_for_multimodal for one sample with one run of <image> placeholders —
     R/model/videogpt_plus/model/arch.py:271-371,453-467.  input_ids [L] (host, with -200) -> embeds [S,D]."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — frames/sec end-to-end (text + masks) of the VideoGLaMM hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--branch framewise|video] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--branch framewise|video] [--full [--no-cpu-baseline] ...]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,8 +18,11 @@ all-gather of the [SEG] embedding; the masks are all-gathered on the devices and
 whole clip (the reference's contract).  --scaling weak: 32 SAM frames PER RANK (clip of 32N frames), LLM side replicated, every
 rank keeps the masks of its own frames (no data-path collective).
 Weights are random-init of the exact architectures (no network / no public Llama VideoGLaMM checkpoint).
-The line is self-checking ("quality"): after the timed region the same clip is re-run ONCE in fp32 parity mode on the
-GPU (same bf16-rounded weights, teacher-forced to the bf16 run's ids) and the bf16 masks / argmaxes are compared with it.
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the headline line, nothing more.
+--full adds, after the timed region: per-kernel rooflines and the per-stage split (extra instrumented passes), the video-branch and
+other-configuration sub-records, the self-check ("quality": the same clip re-run ONCE in fp32 parity mode on the GPU, same
+bf16-rounded weights, teacher-forced to the bf16 run's ids, and the bf16 masks / argmaxes compared with it), the CPU baseline and,
+at N > 1, the per-collective report; the --no-* options switch parts of it off.
 """
 import zlib
 import argparse
@@ -57,12 +60,16 @@ def parse():
     ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: e4m3 weights + row scales in the decode step's MLP GEMVs and the lm_head (decode side of BASELINE config C4's fp8 "
                          "LLM path; NOT the bf16 headline configuration)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-quality", action="store_true", help="skip the fp32 parity-mode re-run that fills the \"quality\" object")
-    ap.add_argument("--no-video-record", action="store_true", help="skip the video-branch sub-run that fills the \"video_branch\" object of a framewise line")
-    ap.add_argument("--video-steps", type=int, default=5, help="timed steps of the video-branch sub-run")
-    ap.add_argument("--no-config-records", action="store_true", help="skip the C1 / C4-clip sub-records of the default (C2) line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: rooflines and stages, the video-branch, "
+                         "C4-clip mask-decoder and C1 / C4-clip records, the fp32 quality self-check, the CPU baseline, the collective report at N > 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the instrumented passes that fill the roofline_* and \"stages\" objects")
+    ap.add_argument("--no-quality", action="store_true", help="--full without the fp32 parity-mode re-run that fills the \"quality\" object")
+    ap.add_argument("--no-video-record", action="store_true",
+                    help="--full without the video-branch sub-run that fills the \"video_branch\" object of a framewise line (and without the records after it)")
+    ap.add_argument("--video-steps", type=int, default=5, help="timed steps of the video-branch sub-run (--full)")
+    ap.add_argument("--no-config-records", action="store_true", help="--full without the C1 / C4-clip sub-records of the default (C2) line")
     ap.add_argument("--llm", default="llama3-8b", choices=["llama3-8b", "phi3-mini"],
                     help="llama3-8b = BASELINE configs C1-C3 (default); phi3-mini = the released checkpoint's LLM")
     ap.add_argument("--tiny", action="store_true", help="plumbing check on a toy architecture (NOT a valid bench)")
@@ -772,28 +779,30 @@ def main():
     if dumped is not None:
         res["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if world > 1:
-        # self-verifying multi-GPU record: the backend, who took part, what the collectives moved and how long the issuing stream spent in them
-        comm.profile = True
-        comm.collective_report()
-        step()                      # one extra pass in the timed (overlapped) configuration, outside the timed region
-        rep = comm.collective_report()
-        comm.profile = False
-        names = sorted(rep)
-        tt = torch.tensor([rep[k]["ms"] for k in names], device=device, dtype=torch.float64)
-        torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
-        for k, v in zip(names, tt.tolist()):
-            rep[k]["ms_max_over_ranks"] = round(v, 3)
+        # self-verifying multi-GPU record: the backend and who took part (gathered before the timed region); --full adds what the collectives
+        # moved and how long the issuing stream spent in them
         uuids = sorted({m["uuid"] or f"device{m['device']}" for m in members})
         res["distributed"] = {"backend": torch.distributed.get_backend() + (" (RCCL)" if torch.distributed.get_backend() == "nccl" else ""),
                               "ranks": members, "distinct_devices": len(uuids), "device_uuids": uuids,
                               "valid_scaling_record": len(uuids) == world and torch.distributed.get_backend() == "nccl",
-                              "plumbing": bool(args.plumbing),
-                              "collectives": {"note": "one extra pass, rank 0's counts; ms = device time between events bracketing the collective on the stream that issues "
-                                                      "it (includes waiting for the slowest rank to arrive); async streamed feature gathers (FrameSharder(stream_features=True) / VG_FEATURES_STREAMED=1, off by default) run from issue to the consuming stream's wait",
-                                              **rep}}
+                              "plumbing": bool(args.plumbing)}
+        if args.full:
+            comm.profile = True
+            comm.collective_report()
+            step()                      # one extra pass in the timed (overlapped) configuration, outside the timed region
+            rep = comm.collective_report()
+            comm.profile = False
+            names = sorted(rep)
+            tt = torch.tensor([rep[k]["ms"] for k in names], device=device, dtype=torch.float64)
+            torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
+            for k, v in zip(names, tt.tolist()):
+                rep[k]["ms_max_over_ranks"] = round(v, 3)
+            res["distributed"]["collectives"] = {"note": "one extra pass, rank 0's counts; ms = device time between events bracketing the collective on the stream that issues "
+                                                         "it (includes waiting for the slowest rank to arrive); async streamed feature gathers (FrameSharder(stream_features=True) / VG_FEATURES_STREAMED=1, off by default) run from issue to the consuming stream's wait",
+                                                 **rep}
         if len(uuids) != world:
             res["distributed"]["warning"] = f"{world} ranks on {len(uuids)} device(s): ranks time-slice GPUs — NOT a scaling measurement"
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # (every rank runs these extra steps — a step contains the frame-sharding collectives — rank 0 reports)
         # instrumented extra step (not part of the timed region): per-launch HIP events on the launch stream.  It runs
         # with the Hiera/LLM stream overlap switched off: an event pair on one of two concurrently fed streams also
@@ -973,20 +982,20 @@ def main():
             res["roofline_decode"] = {"bound": "hbm", "kernel": "decode step (HIP graph: decode_gemv_fast_kernel x4 (q|k|v with RoPE + append) + decode_attn2_kernel per layer)",
                                       "achieved": round(tbs * 1e3, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(tbs / 8.0, 4),
                                       "algorithmic_bytes_per_step": round(wbytes), "steps": dec_n, "ms_per_token": round(dec_ms / dec_n, 3)}
-    if world == 1 and not use_video and not args.tiny and not args.no_video_record:
+    records = args.full and world == 1 and not use_video and not args.tiny and not args.no_video_record
+    if records:
         res["video_branch"] = video_record(args, model, ops, (images, context, sam, ids))
-    if world == 1 and not use_video and not args.tiny and not args.no_video_record:
         res["roofline_mask_decoder_c4clip"] = mask_decoder_record(model, device)
     is_c2 = (args.frames, args.src, args.objects, args.te) == (32, 1024, 1, 16) and args.llm == "llama3-8b" and (args.decode_weights, args.prefill) == ("bf16", "bf16")
-    if world == 1 and not use_video and not args.tiny and not args.no_config_records and not args.no_video_record and is_c2:
+    if records and not args.no_config_records and is_c2:
         # the other single-GPU configurations of BASELINE.json on the same model, 3 timed steps each (C3 / C4's 8-GPU split need the node)
         res["configs"] = {"note": "BASELINE configs beside the headline (C2), timed after it on the same loaded model: inputs in HBM -> ids + masks on the host",
                           "c1": config_record(args, cfg, model, device, 8, 512, 1, 8),
                           "c4_clip_one_gpu_bf16": config_record(args, cfg, model, device, 64, 1024, 8, 16),
                           "c4_clip_one_gpu_fp8_llm": config_record(args, cfg, model, device, 64, 1024, 8, 16, fp8=True)}
-    if world == 1 and not args.no_quality and not args.tiny:
+    if args.full and world == 1 and not args.no_quality and not args.tiny:
         res["quality"] = quality(cfg, args, model, step, device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tiny:      # the CPU leg runs at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tiny:      # the CPU leg runs at N = 1 only
         res["cpu_baseline"] = cpu_baseline(cfg, args)
     if rank == 0:
         print(json.dumps(res), flush=True)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs ON the GPU box (gpurun -- 'bash tools/collect_profiles.sh TAG [all|kt|pmc|mfma|bench]'): the bench lines and rocprofv3 passes that
 # profiles/ is made from.  Outputs under gpurun_out/TAG_*.
-#   bench: bench.py defaults (C2 framewise, quality + cpu_baseline included), run AFTER the traces -> TAG_bench.json
+#   bench: bench.py --full (C2 framewise, quality + cpu_baseline included), run AFTER the traces -> TAG_bench.json
 #   kt:    TWO kernel traces of `bench.py --steps 3 --warmup 1 --no-roofline ...` (4 passes each, nothing else in the process):
 #          the timed stream configuration (Hiera on its side stream)                     -> TAG_kt_overlapped.txt / .json
 #          VG_HIERA_START=serial VG_TOWERS_OVERLAP=0 (the instrumented pass's config)    -> TAG_kt_serial.txt / .json
@@ -44,7 +44,7 @@ if has bench; then
 # after the traces: the line quotes profiles/${TAG}_kt_*.json (frac_trace_*, mfma_busy_frac_*), so the traces of THIS call (same box, same build) go
 # into the box's copy of profiles/ first
 for MODE in overlapped serial; do [ -f $O/${TAG}_kt_$MODE.json ] && cp $O/${TAG}_kt_$MODE.json $R/profiles/; done
-python $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 tail -c 900 $O/${TAG}_bench.json
 fi
 if has pmc; then
@@ -62,13 +62,13 @@ rm -rf $O/${TAG}_pmc_fetch $O/${TAG}_pmc_write          # the databases are larg
 fi
 [ $ONLY = all ] || exit 0
 
-python $R/bench.py --branch video --no-cpu-baseline > $O/${TAG}_bench_video.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --frames 8 --te 8 --src 512 --no-cpu-baseline --no-video-record > $O/${TAG}_bench_c1.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --llm phi3-mini --no-cpu-baseline --no-video-record > $O/${TAG}_bench_phi3.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --branch video --no-cpu-baseline > $O/${TAG}_bench_video.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --frames 8 --te 8 --src 512 --no-cpu-baseline --no-video-record > $O/${TAG}_bench_c1.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --llm phi3-mini --no-cpu-baseline --no-video-record > $O/${TAG}_bench_phi3.json 2>> $O/${TAG}_bench.err
 # BASELINE config C4's clip on ONE GPU (64 frames, 8 [SEG] objects = 512 mask-decoder instances), bf16 and the fp8 LLM path, framewise and video branch
-python $R/bench.py --frames 64 --objects 8 --no-cpu-baseline --no-quality --no-video-record > $O/${TAG}_bench_c4clip.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --frames 64 --objects 8 --prefill fp8 --decode-weights fp8 --no-cpu-baseline --no-quality --no-video-record > $O/${TAG}_bench_c4clip_fp8.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --frames 64 --objects 8 --branch video --no-cpu-baseline --no-quality --steps 2 > $O/${TAG}_bench_c4clip_video.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --frames 64 --objects 8 --no-cpu-baseline --no-quality --no-video-record > $O/${TAG}_bench_c4clip.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --frames 64 --objects 8 --prefill fp8 --decode-weights fp8 --no-cpu-baseline --no-quality --no-video-record > $O/${TAG}_bench_c4clip_fp8.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --frames 64 --objects 8 --branch video --no-cpu-baseline --no-quality --steps 2 > $O/${TAG}_bench_c4clip_video.json 2>> $O/${TAG}_bench.err
 cut -c1-140 $O/${TAG}_bench_video.json $O/${TAG}_bench_c1.json $O/${TAG}_bench_phi3.json $O/${TAG}_bench_c4clip.json $O/${TAG}_bench_c4clip_fp8.json $O/${TAG}_bench_c4clip_video.json
 # r05: the video branch (kernel trace of the C2 clip and of C4's clip on it, one tracked frame kernel by kernel), the mask decoder at C4's clip size, GEMMs against the vendor library
 P=${TAG%_c2}

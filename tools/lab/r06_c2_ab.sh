@@ -1,7 +1,7 @@
 #!/bin/bash
 # C2 clip with / without the r06 decode launches and the run-ahead loop, same box: ms per step + the serial decode stage
 cd "$(dirname "$0")/../.."
-run() { env "$@" python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-quality --no-video-record 2>/dev/null | python -c "
+run() { env "$@" python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-quality --no-video-record 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], 'decode stage', d['stages']['decode']['ms'], 'ms/token', d['roofline_decode']['ms_per_token'])"; }
 for rep in 1 2; do

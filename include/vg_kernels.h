@@ -232,7 +232,7 @@ int vg_decode_advance(int64_t* tok, int* pos, int* step, const int64_t* forced, 
                       const float* cos, const float* sin, float* rope_cs, int half_dim, int inc, vg_stream_t stream);
 /* The batched multi-prompt decode step: B <= 16 rows, each bit-identical to the single-row kernel on that row alone.
  * vg_decode_rows_supported: 1 when the B-row kernels below cover a bf16 Llama layer of this shape (head_dim 128; hidden / inter multiples of 2048).
- * vg_decode_gemv_rows: vg_decode_gemv for B rows x[b] = x + b * ldx -> y + b * ldy (residual R + b * ldr); bf16 only.
+ * vg_decode_gemv_rows: vg_decode_gemv for B rows x[b] = x + b * ldx -> y + b * ldy (residual R + b * ldr); bf16 only, K = 3072 or 2048 x {1, 2, 4, 7, 8}.
  * vg_decode_qkv_rope_rows: vg_decode_qkv_rope for B rows: row b at position pos[b] with rope_cs + b * D (cos row | sin row), q -> q_out + b * ldq,
  *   its key / value rows into slot b: k_slots / v_slots + b * slot_stride + (pos[b] - row0) * Hkv * D (rows clamped to [0, slot_rows)).
  * vg_decode_attention2_rows: vg_decode_attention2 for B rows (q / out rows of H * D); key rows below row0 (a multiple of keys_per_wg) from
@@ -255,6 +255,22 @@ int vg_decode_step_begin_rows(const int64_t* tok, const void* table, void* x, in
                               float* rope_cs, int half_dim, int B, vg_stream_t stream);
 int vg_decode_step_end_rows(uint64_t* acc, int64_t* tok, int* pos, int* step, const int64_t* forced, int n_forced, int64_t* hist, int64_t* raw,
                             int cap, const void* row, void* hid, int64_t hid_stride, int hid_row0, int hid_rows, int D, int dtype, int B, vg_stream_t stream);
+/* The batched step of the decode_attention path (Phi-3-mini width), each row bit-identical to the single-row kernel on it alone.
+ * vg_decode_attention_rows_supported: 1 when vg_decode_attention_rows covers the shape (bf16, MHA, head_dim 96).
+ * vg_decode_step_rows_supported: 1 when the B-row kernels cover a whole layer of the decode_attention step: the attention above, hidden = H * D
+ *   (q|k|v, o, gate|up GEMVs) and inter (down) row lengths of vg_decode_gemv_rows.
+ * vg_decode_attention_rows: vg_decode_attention for B rows: row b's q|k|v row at qkv + b * ldqkv, RoPE at pos[b] (cos / sin: [>= max_len, D / 2]),
+ *   its new key / value row appended into slot b: k_slots / v_slots + b * slot_stride + (pos[b] - row0) * Hkv * D; key rows below row0 (a multiple
+ *   of 128) from k_cache / v_cache ([max_len, Hkv, D], shared), rows from row0 on from slot b; output row b at out + b * H * D.  Keys per workgroup
+ *   of row b: 128 when pos[b] >= kpw_min, else 64.  n_bound: every pos[b] < n_bound <= min(row0 + slot_rows, max_len) (a row outside
+ *   [row0, n_bound) is skipped).  workspace: vg_decode_attention_rows_ws_floats() floats, zero-filled once (self-resetting counters). */
+int vg_decode_attention_rows_supported(int H, int Hkv, int D, int dtype);
+int vg_decode_step_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype);
+int64_t vg_decode_attention_rows_ws_floats(int H, int Hkv, int D, int n_bound, int B);
+int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots, void* v_slots,
+                             int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out, int H, int Hkv, int D,
+                             int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace, int64_t ws_floats, int B, int dtype,
+                             vg_stream_t stream);
 /* Sampled decoding (csrc/vg_sample.hip): HF's Temperature -> TopK -> TopP warpers and the draw on one fp32 logits row x[n]
  *   (n < 2^22), one launch.  params: the 24-byte device block {float T; float p; int k; int pad; uint64 seed} (k = 0: no top-k; p = 1: no top-p).
  * vg_sample_partial — acc[0] = the drawn entry's packed (ordered value bits, ~index) key, the hand-off vg_argmax_partial leaves, so

@@ -7,7 +7,7 @@ differ in their 30 question ids.  One JSON line per LLM:
   "sequential_ms"[B]: ms for the same B prompts as B inference() calls
   "ratio"[B]:         prompts_ms / sequential_ms
   "decode_step_ms":   one replayed decode step of one prompt (LlamaDecoder.decode_step, the step the sequential loop decodes with), ms per token
-  "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode; Llama-3 width only), ms per step
+  "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode: Llama-3 and Phi-3-mini widths), ms per step
 --ab also times inference_prompts() with VG_PROMPTS_BATCHED=0 ("prompts_seq_ms"[B]: the prompts decoded one after another).
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 

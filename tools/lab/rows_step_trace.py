@@ -1,0 +1,47 @@
+"""Kernel-trace driver of the batched decode step: 8 prompts through prompts.generate_prompts at full Phi-3-mini width (32 layers, bf16 synthetic weights), prefix P = 1700 rows,
+then 24 replayed B = 8 batched steps (the dispatches a kernel trace then cuts out: the last 24 steps)."""
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from videoglamm_amd import synth  # noqa: E402
+from videoglamm_amd.params import Params  # noqa: E402
+from videoglamm_amd.prompts import generate_prompts  # noqa: E402
+
+torch.set_grad_enabled(False)
+
+
+class Towers:
+    def __init__(self, v):
+        self.v = v
+
+    def encode(self, *a):
+        return self.v
+
+
+dev = torch.device("cuda", 0)
+full = synth.videoglamm_phi3_mini()
+man = {k: v for k, v in synth.vlm_manifest(full).items()
+       if k.startswith(("model.layers.", "model.norm", "model.embed_tokens", "lm_head", "model.text_hidden_fcs"))}
+P = Params(synth.device_state_dict(man, dev, torch.bfloat16), dev, torch.bfloat16)
+c = full["llm"]
+g = torch.Generator().manual_seed(1)
+nvis = 1697
+visual = (torch.randn(nvis, c["hidden"], generator=g) * 0.5).to(torch.bfloat16).to(dev)
+head = torch.tensor([1, 5, 6, -200])
+ids = [torch.cat([head, torch.randint(3, c["vocab"] - 2, (30,), generator=g)]) for _ in range(8)]
+cfg = dict(llm=c, seg_token_idx=full["seg_token_idx"])
+generate_prompts(P, cfg, Towers(visual), None, None, ids, 32)
+rows = next(iter(P._decoder._rows.values()))
+print(f"row0 {rows.row0} n_bound {rows.n_bound} start_pos {rows.start_pos} B {rows.B} attn_rows {rows.attn_rows}", flush=True)
+rows.set_positions(rows.start_pos)
+rows.decode_step()
+torch.cuda.synchronize()
+t = time.perf_counter()
+for _ in range(24):
+    rows.decode_step()
+torch.cuda.synchronize()
+print(f"ms per replayed step: {(time.perf_counter() - t) * 1000 / 24:.3f}", flush=True)

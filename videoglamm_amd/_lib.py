@@ -60,6 +60,10 @@ def _sig(lib):
         "vg_decode_attention2_rows": ([P, P, P, I, P, P, L, I, I, P, I, I, I, I, I, F, P, P, L, I, I, I, P], c_int),
         "vg_decode_step_begin_rows": ([P, P, P, I, I, P, P, P, P, I, I, P], c_int),
         "vg_decode_step_end_rows": ([P, P, P, P, P, I, P, P, I, P, P, L, I, I, I, I, I, P], c_int),
+        "vg_decode_attention_rows_supported": ([I, I, I, I], c_int),
+        "vg_decode_step_rows_supported": ([I, I, I, I, I, I], c_int),
+        "vg_decode_attention_rows_ws_floats": ([I, I, I, I, I], c_int64),
+        "vg_decode_attention_rows": ([P, L, P, P, I, P, P, L, I, I, P, P, P, I, I, I, I, I, F, P, I, P, L, I, I, P], c_int),
         "vg_sample_workspace_ints": ([], c_int),
         "vg_sample_partial": ([P, I, P, P, P, P, P, P, P], c_int),
         "vg_sample_survivors": ([P, I, P, P, P, I, P, P], c_int),

@@ -503,6 +503,8 @@ extern "C" int vg_decode_qkv_rope(const void* x, const void* Wqkv, int64_t ldw, 
 // dec_dot in that order, the same wave_sum and the same epilogue — so row r of the result is bit-identical to vg_decode_gemv on row r alone.
 // Which wave owns which pair does not enter the sums (the split is free).  x is staged into LDS as bf16 rows; when B x K x 2 bytes exceed the
 // budget the K batches are staged in phases and each wave owns one pair, its accumulators carried across the phases (the order stays).
+// NB = 3, CPB = 2 (K = 3072, Phi-3-mini's hidden size): decode_gemv_fast_kernel<..., 3, 2>'s walk — batches of 128 chunks (chunk u: lane + 64 u + 128 cb)
+// and a norm prologue whose second chunk per thread is partial (threads 0..127 only).
 constexpr int DEC_ROWS_PPW = 8, DEC_ROWS_LDS = 64 * 1024;
 
 struct DecRowsArgs {
@@ -512,21 +514,24 @@ struct DecRowsArgs {
   const float* rope_cs; const int* pos; void* kc; void* vc; int64_t slot_stride; int row0, slot_rows, H, Hkv;
 };
 
+template <int NB> constexpr int dec_rows_cpb() { return NB == 3 ? 2 : 4; }     // chunks per lane per batch: 2 only at K = 3072
+
 template <typename TO, bool GLU, int NB, int BR, int RHD>
 __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
   typedef bf16_t T;
-  constexpr int CPB = 4, KPC = 8, NWV = 2;
-  constexpr int NCH = NB * CPB * 64, XN = NCH / 256;
+  constexpr int CPB = dec_rows_cpb<NB>(), KPC = 8, NWV = 2;
+  constexpr int BC = CPB * 64;                     // chunks per batch
+  constexpr int NCH = NB * BC, XN = (NCH + 255) / 256;     // the last chunk per thread may be partial (NCH % 256 == 128)
   extern __shared__ __attribute__((aligned(16))) char dec_smem[];
   __shared__ float red[BR][4];
   __shared__ float res[4][DEC_ROWS_PPW][BR][2];
-  u32x4_t* xs = (u32x4_t*)dec_smem;                // [BR][nph * 256] chunks of the current phase
+  u32x4_t* xs = (u32x4_t*)dec_smem;                // [BR][nph * BC] chunks of the current phase
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int npair = RHD > 0 ? p.N / 2 : GLU ? p.N : (p.N + 1) / 2;
   const int p0 = (blockIdx.x * 4 + wave) * p.ppw;
   const int np = max(min(p0 + p.ppw, npair) - p0, 0);
   const T* W = (const T*)p.W;
-  const int pch = p.nph * 256;                     // chunks per row per phase
+  const int pch = p.nph * BC;                      // chunks per row per phase
 
   float rstd[BR];
 #pragma unroll
@@ -538,10 +543,12 @@ __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
       float ss = 0.f;
 #pragma unroll
       for (int i = 0; i < XN; ++i) {
-        float f[KPC];
-        dec_unpack<T>(xg[tid + 256 * i], f);
+        if (NCH % 256 == 0 || tid + 256 * i < NCH) {
+          float f[KPC];
+          dec_unpack<T>(xg[tid + 256 * i], f);
 #pragma unroll
-        for (int e = 0; e < KPC; ++e) ss += f[e] * f[e];
+          for (int e = 0; e < KPC; ++e) ss += f[e] * f[e];
+        }
       }
       ss = wave_sum(ss);
       if (lane == 0) red[r][wave] = ss;
@@ -557,9 +564,9 @@ __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
   for (int ph = 0; ph < NB; ph += p.nph) {
     const int nbp = min(p.nph, NB - ph);
     if (ph > 0) __syncthreads();                   // every wave is done with the previous phase's rows
-    // ---- stage rows' chunks [ph * 256, (ph + nbp) * 256)
-    for (int c = tid; c < nbp * 256; c += 256) {
-      const int gc = ph * 256 + c;
+    // ---- stage rows' chunks [ph * BC, (ph + nbp) * BC)
+    for (int c = tid; c < nbp * BC; c += 256) {
+      const int gc = ph * BC + c;
 #pragma unroll
       for (int r = 0; r < BR; ++r) {
         u32x4_t v = ((const u32x4_t*)((const T*)p.x + (int64_t)min(r, p.B - 1) * p.ldx))[gc];
@@ -655,28 +662,34 @@ __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
   }
 }
 
-static int dec_rows_nb(int K) {
+// batches per row at K = 2048 x {1, 2, 4, 7, 8} (four chunks per lane per batch)
+static int dec_rows_nb4(int K) {
   const int nch = K / 8;
   if (K % 2048) return 0;
   const int nb = nch / 256;
   return nb == 1 || nb == 2 || nb == 4 || nb == 7 || nb == 8 ? nb : 0;
 }
 
+static int dec_rows_nb(int K) {
+  return K == 3072 ? 3 : dec_rows_nb4(K);         // 3072 (Phi-3-mini's hidden size): three batches of two chunks per lane (CPB = 2)
+}
+
 extern "C" int vg_decode_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype) {
-  return dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, hidden, dtype) && dec_rows_nb(hidden) && dec_rows_nb(inter) && (H * D) == hidden;
+  return dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, hidden, dtype) && dec_rows_nb4(hidden) && dec_rows_nb4(inter) && (H * D) == hidden;
 }
 
 template <typename TO, bool GLU, int NB, int BR, int RHD>
 static int launch_rows_b(DecRowsArgs p, hipStream_t st) {
   const int npair = RHD > 0 ? p.N / 2 : GLU ? p.N : (p.N + 1) / 2;
+  constexpr int BBYTES = dec_rows_cpb<NB>() * 64 * 16;     // bytes of one row's batch of chunks
   // x staging: the whole row when it fits the budget (always with the norm), else phases of batches with one pair per wave
   int nph = NB;
-  if (!p.nw && (int64_t)BR * NB * 4096 > DEC_ROWS_LDS) nph = max(1, DEC_ROWS_LDS / (BR * 4096));
+  if (!p.nw && (int64_t)BR * NB * BBYTES > DEC_ROWS_LDS) nph = max(1, DEC_ROWS_LDS / (BR * BBYTES));
   int ppw = (npair + 2047) / 2048;                  // ~2 workgroups per CU, as vg_decode_gemv
   ppw = nph < NB ? 1 : min(ppw, DEC_ROWS_PPW);
   p.nph = nph;
   p.ppw = ppw;
-  const size_t lds = (size_t)BR * nph * 4096;
+  const size_t lds = (size_t)BR * nph * BBYTES;
   static size_t cap = 64 * 1024;
   if (lds > 64 * 1024 && lds > cap) {
     (void)hipFuncSetAttribute((const void*)decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -700,6 +713,7 @@ template <bool GLU>
 static int launch_rows(DecRowsArgs p, hipStream_t st) {
   switch (dec_rows_nb(p.K)) {
     case 1: return launch_rows_nb<bf16_t, GLU, 1, 0>(p, st);
+    case 3: return launch_rows_nb<bf16_t, GLU, 3, 0>(p, st);
     case 2: return launch_rows_nb<bf16_t, GLU, 2, 0>(p, st);
     case 4: return launch_rows_nb<bf16_t, GLU, 4, 0>(p, st);
     case 7: return launch_rows_nb<bf16_t, GLU, 7, 0>(p, st);
@@ -710,7 +724,7 @@ static int launch_rows(DecRowsArgs p, hipStream_t st) {
 extern "C" int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
                                    const void* R, int64_t ldr, int N, int K, int B, int glu, int dtype, vg_stream_t stream) {
   VG_CHECK(x && W && y && N > 0 && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemv_rows: bad args N=%d B=%d", N, B);
-  VG_CHECK(dtype == VG_BF16 && dec_rows_nb(K), VG_ERR_UNSUPPORTED, "vg_decode_gemv_rows: bf16 rows of K = 2048 x {1, 2, 4, 7, 8} only (K=%d dtype=%d)", K, dtype);
+  VG_CHECK(dtype == VG_BF16 && dec_rows_nb(K), VG_ERR_UNSUPPORTED, "vg_decode_gemv_rows: bf16 rows of K = 3072 or 2048 x {1, 2, 4, 7, 8} only (K=%d dtype=%d)", K, dtype);
   VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)W) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
            "vg_decode_gemv_rows: alignment (16 bytes; ldx / ldw multiples of 8)");
   const int br = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;      // the bucket the kernel stages
@@ -1135,6 +1149,90 @@ extern "C" int vg_decode_attention(const void* qkv, void* k_cache, void* v_cache
   DecAttnArgs p{qkv, k_cache, v_cache, cos, sin, out, workspace, (int*)(workspace + (need - Hkv)), pos_dev, H, Hkv, D, nsplit, scale, window};
   if (dtype == VG_BF16) return launch_decode_attn<bf16_t>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
   return launch_decode_attn<float>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// B query rows of vg_decode_attention at once (the batched multi-prompt decode step of the decode_attention path): grid z = row.
+// Row b is decode_attn_kernel on row b alone — its q|k|v row (qkv + b * ldqkv), RoPE at pos[b] from the shared cos / sin tables, the append of
+// its new key / value row, its own partials, arrival counters and output row — so it is bit-identical to vg_decode_attention on that row with the
+// whole cache in one array.  Key blocks below row0 come from the shared caches (the prefix); blocks from row0 on are slot b's (ks / vs +
+// b * slot_stride, sequence row j at j - row0), and the new rows are appended there.  row0 is a multiple of 128, so every 64- or 128-key split is
+// wholly shared or wholly per slot.  Keys per workgroup: 128 (LB = 2) when pos[b] >= kpw_min, else 64 — the single-row step's choice, made per
+// row on the device, so rows on both sides of the threshold share one launch and one captured graph.  A row whose position lies outside
+// [row0, n_bound) does nothing (no append, no counter touched; RowsDecode refuses such a step on the host).
+struct DecAttnRowsArgs {
+  void* ks; void* vs; int64_t slot_stride, ldqkv, ws_row; const int* pos; int row0, n_bound, kpw_min;
+};
+
+template <int G, int DT>
+__global__ __launch_bounds__(256) void decode_attn_rows_kernel(DecAttnArgs p, DecAttnRowsArgs r) {
+  extern __shared__ __attribute__((aligned(16))) char dec_smem[];
+  __shared__ int ticket;
+  const int b = blockIdx.z, s = blockIdx.x, kvh = blockIdx.y;
+  const int pos = r.pos[b];
+  if (pos < r.row0 || pos >= r.n_bound) return;
+  const bool wide = pos >= r.kpw_min;              // uniform across the workgroup
+  DecAttnArgs q = p;
+  q.qkv = (const bf16_t*)p.qkv + b * r.ldqkv;
+  q.o = (bf16_t*)p.o + (int64_t)b * p.H * DT;
+  q.ws = p.ws + b * r.ws_row;
+  q.cnt = p.cnt + b * p.Hkv;
+  q.pos_dev = r.pos + b;
+  if (s * (wide ? 128 : 64) >= r.row0) {           // a per-slot split: the body's row j lands on slot row j - row0 (j >= row0 only)
+    const int64_t off = b * r.slot_stride - (int64_t)r.row0 * p.Hkv * DT;
+    q.kc = (bf16_t*)r.ks + off;
+    q.vc = (bf16_t*)r.vs + off;
+  }
+  if (wide) dec_attn_body<bf16_t, G, DT, false, 2>(q, s, kvh, dec_smem, ticket, nullptr);
+  else dec_attn_body<bf16_t, G, DT, false, 1>(q, s, kvh, dec_smem, ticket, nullptr);
+}
+
+extern "C" int vg_decode_attention_rows_supported(int H, int Hkv, int D, int dtype) {
+  return dtype == VG_BF16 && H > 0 && H == Hkv && D == 96;       // Phi-3-mini: MHA, head_dim 96
+}
+
+extern "C" int vg_decode_step_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype) {
+  // the decode_attention step's layer on the B-row kernels: the attention above, the q|k|v / o / gate|up GEMVs at K = hidden (the norm stages the
+  // 16-row bucket's whole rows) and down at K = inter
+  return vg_decode_attention_rows_supported(H, Hkv, D, dtype) && H * D == hidden && dec_rows_nb(hidden) && dec_rows_nb(inter) &&
+         16 * hidden * 2 <= 160 * 1024 - 8 * 1024;
+}
+
+extern "C" int64_t vg_decode_attention_rows_ws_floats(int H, int Hkv, int D, int n_bound, int B) {
+  if (H <= 0 || Hkv <= 0 || D <= 0 || n_bound <= 0 || B <= 0 || H % Hkv) return -1;
+  const int64_t nsplit = (n_bound + 63) / 64;
+  return (int64_t)B * Hkv * nsplit * (H / Hkv) * (D + 2) + (int64_t)B * Hkv;
+}
+
+extern "C" int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots,
+                                        void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out,
+                                        int H, int Hkv, int D, int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace,
+                                        int64_t ws_floats, int B, int dtype, vg_stream_t stream) {
+  VG_CHECK(qkv && k_cache && v_cache && k_slots && v_slots && cos && sin && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG,
+           "vg_decode_attention_rows: bad args B=%d", B);
+  VG_CHECK(vg_decode_attention_rows_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "vg_decode_attention_rows: H=%d Hkv=%d D=%d dtype=%d not covered",
+           H, Hkv, D, dtype);
+  VG_CHECK(row0 >= 0 && row0 % 128 == 0 && slot_rows > 0 && n_bound > row0 && n_bound <= row0 + slot_rows && n_bound <= max_len && window >= 0 &&
+               ldqkv >= (int64_t)(H + 2 * Hkv) * D, VG_ERR_ARG,
+           "vg_decode_attention_rows: row0=%d (a multiple of 128), slot_rows=%d, n_bound=%d in (row0, min(row0 + slot_rows, max_len %d)]", row0,
+           slot_rows, n_bound, max_len);
+  VG_CHECK((((uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k_slots | (uintptr_t)v_slots) & 15) == 0 && slot_stride % 8 == 0 &&
+               slot_stride >= (int64_t)slot_rows * Hkv * D, VG_ERR_ARG, "vg_decode_attention_rows: 16-byte alignment; slots must not overlap");
+  const int64_t need = vg_decode_attention_rows_ws_floats(H, Hkv, D, n_bound, B);
+  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention_rows: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
+  const int nsplit = (n_bound + 63) / 64;
+  VG_CHECK(nsplit <= 128, VG_ERR_UNSUPPORTED, "vg_decode_attention_rows: n_bound %d > 8192", n_bound);
+  const int G = H / Hkv;
+  const int64_t ws_row = (int64_t)Hkv * nsplit * G * (D + 2);
+  DecAttnArgs p{qkv, (void*)k_cache, (void*)v_cache, cos, sin, out, workspace, (int*)(workspace + (ws_floats - (int64_t)B * Hkv)), pos, H, Hkv, D,
+                nsplit, scale, window};
+  DecAttnRowsArgs r{k_slots, v_slots, slot_stride, ldqkv, ws_row, pos, row0, n_bound, kpw_min};
+  // the LB = 2 layout (launch_decode_attn's, plus the second block's scores): LB = 1 rows use a prefix of it
+  const int KP = 256 / (D / 8);
+  const size_t lds = sizeof(float) * ((size_t)G * D + 2 * D + 4 * G * 64 + G * 64 + 2 * G + 4 + (size_t)KP * G * D + 4 * G * 64 + G * 64);
+  decode_attn_rows_kernel<1, 96><<<dim3(nsplit, Hkv, B), 256, lds, (hipStream_t)stream>>>(p, r);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

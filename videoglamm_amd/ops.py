@@ -863,6 +863,35 @@ def decode_attention2_rows(q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, 
     return out
 
 
+def decode_step_rows_supported(H, Hkv, D, hidden, inter, dtype):
+    """True when the B-row kernels cover a layer of the decode_attention step (vg_decode_step_rows_supported: bf16 Phi-3-mini width, MHA, head_dim 96)."""
+    return dtype == torch.bfloat16 and bool(_lib.load().vg_decode_step_rows_supported(H, Hkv, D, hidden, inter, BF16))
+
+
+def decode_attention_rows_workspace(H, Hkv, D, n_bound, B, device):
+    n = _lib.load().vg_decode_attention_rows_ws_floats(H, Hkv, D, int(n_bound), int(B))
+    if n < 0:
+        raise _lib.VGKernelError(f"vg_decode_attention_rows_ws_floats: bad shape H={H} Hkv={Hkv} D={D} n_bound={n_bound} B={B}")
+    return torch.zeros(n, dtype=torch.float32, device=device)
+
+
+def decode_attention_rows(qkv, k_cache, v_cache, k_slots, v_slots, row0, cos, sin, H, Hkv, D, pos_dev, n_bound, scale, ws, window=0, kpw_min=2048):
+    """decode_attention on each row of qkv [B, (H+2Hkv)*D] (vg_decode_attention_rows): row b RoPE'd at pos_dev[b], its K / V rows appended into slot b
+    of k_slots / v_slots ([B, rows, Hkv, D], sequence row j at j - row0), keys [0, row0) from the shared caches; 128 keys per workgroup for the rows
+    at pos_dev[b] >= kpw_min -> [B, H*D]."""
+    lib = _lib.load()
+    B = qkv.shape[0]
+    assert qkv.stride(1) == 1 and k_cache.is_contiguous() and v_cache.is_contiguous() and k_slots.is_contiguous() and v_slots.is_contiguous()
+    assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= B and k_slots.shape[0] >= B and k_slots.shape == v_slots.shape
+    assert k_slots.shape[2:] == (Hkv, D) and qkv.shape[1] == (H + 2 * Hkv) * D
+    out = torch.empty(B, H * D, dtype=qkv.dtype, device=qkv.device)
+    rc = lib.vg_decode_attention_rows(_p(qkv), qkv.stride(0), _p(k_cache), _p(v_cache), k_cache.shape[0], _p(k_slots), _p(v_slots), k_slots.stride(0),
+                                      int(row0), k_slots.shape[1], _p(_f32(cos)), _p(_f32(sin)), _p(out), H, Hkv, D, int(n_bound), int(window),
+                                      float(scale), _p(pos_dev), int(kpw_min), _p(ws), ws.numel(), B, _dt(qkv), _stream())
+    _lib.check(rc, "vg_decode_attention_rows")
+    return out
+
+
 def decode_step_begin_rows(tok_dev, table, pos_dev, rope=None):
     """decode_step_begin per row: x[b] = table[tok_dev[b]] -> [B, D]; rope = (cos, sin, rope_cs [B, 2*half]): rope_cs[b] = cos / sin rows of pos_dev[b]."""
     lib = _lib.load()

@@ -495,13 +495,20 @@ class RowsDecode:
     Key / value rows below row0 = floor(P / kw) * kw (kw = the attention's keys per workgroup) are read from the decoder's caches; every row b has its
     own zero-filled slot of rows [row0, n_bound) (the straddling block [row0, P) copied in once, then its suffix prefill and its decode rows), its
     own final-norm rows (hid[b], position p at p - row0), token, position, step counter, accumulator, forcing table and sampling parameter block.
+    Two forms of the step, as the decoder's single-row step: the rope path (bf16 head_dim 128: q|k|v + RoPE + append, then vg_decode_attention2_rows;
+    kw = dec.kpw2) and the decode_attention path (Phi-3-mini width: q|k|v GEMV, then RoPE + append + attention in vg_decode_attention_rows, whose
+    rows pick 64 or 128 keys per workgroup on the device from their own position and dec.kpw_min; kw = ATTN_KW).
     The step is captured once per sampling route ("greedy" / "sample_fast" / "sample") into a HIP graph; a new seed or temperature is a copy into
     samp_params.  Rows past the live prompts (bucket padding) and retired rows keep computing into their own slots; their tokens are ignored."""
+
+    ATTN_KW = 128      # the decode_attention path's largest split: row0 a multiple of it keeps 64- and 128-key splits wholly shared or per slot
 
     def __init__(self, dec, bucket, row0, n_bound):
         self.dec, self.B, self.row0, self.n_bound = dec, bucket, row0, n_bound
         d, dev, dt = dec, dec.P.device, dec.P.dtype
         B = bucket
+        self.attn_rows = not d.rope_path
+        assert row0 % (self.ATTN_KW if self.attn_rows else d.kpw2) == 0
         rows = n_bound - row0
         self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
         self.vs = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
@@ -516,7 +523,10 @@ class RowsDecode:
         self.rope_cs = torch.zeros(B, d.hd, dtype=torch.float32, device=dev)
         self.samp_params = torch.zeros(B, 6, dtype=torch.int32, device=dev)
         self.samp_ws = None
-        self.attn_ws = ops.decode_attention2_rows_workspace(d.H, d.Hkv, d.hd, n_bound, d.kpw2, B, dev)
+        if self.attn_rows:
+            self.attn_ws = ops.decode_attention_rows_workspace(d.H, d.Hkv, d.hd, n_bound, B, dev)
+        else:
+            self.attn_ws = ops.decode_attention2_rows_workspace(d.H, d.Hkv, d.hd, n_bound, d.kpw2, B, dev)
         self.route = "greedy"
         self.graphs = {}
         self.steps = 0          # replayed (or eager) steps since the object was made: the batched loop's step count
@@ -551,14 +561,20 @@ class RowsDecode:
 
     def _step(self):
         d, P, c = self.dec, self.dec.P, self.dec.c
-        x = ops.decode_step_begin_rows(self.tok, P.t("model.embed_tokens.weight"), self.pos, rope=(d.cos, d.sin, self.rope_cs))
+        x = ops.decode_step_begin_rows(self.tok, P.t("model.embed_tokens.weight"), self.pos,
+                                       rope=None if self.attn_rows else (d.cos, d.sin, self.rope_cs))
         for i in range(c["num_layers"]):
             l = f"model.layers.{i}."
             wqkv, _ = P.fused([l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"], stored=l + "self_attn.qkv_proj")
-            q = ops.decode_qkv_rope_rows(x, wqkv, P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i], self.row0, self.rope_cs,
-                                         self.pos, d.H, d.Hkv, d.hd)
-            o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
-                                           d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
+            if self.attn_rows:
+                qkv = ops.decode_gemv_rows(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
+                o = ops.decode_attention_rows(qkv, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.cos, d.sin, d.H, d.Hkv, d.hd, self.pos,
+                                              self.n_bound, d.hd ** -0.5, self.attn_ws, window=d.window, kpw_min=d.kpw_min)
+            else:
+                q = ops.decode_qkv_rope_rows(x, wqkv, P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i], self.row0,
+                                             self.rope_cs, self.pos, d.H, d.Hkv, d.hd)
+                o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
+                                               d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
             x = ops.decode_gemv_rows(o, P.w(l + "self_attn.o_proj"), residual=x)
             wgu, _ = P.fused([l + "mlp.gate_proj", l + "mlp.up_proj"], stored=l + "mlp.gate_up_proj")
             a = ops.decode_gemv_rows(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)

@@ -244,6 +244,16 @@ int vg_decode_advance(int64_t* tok, int* pos, int* step, const int64_t* forced, 
 int vg_decode_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype);
 int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
                         const void* R, int64_t ldr, int N, int K, int B, int glu, int dtype, vg_stream_t stream);
+/* vg_decode_gemv_w8 for B rows (the MLP and the lm_head of the batched step with fp8 decode weights): x[b] = x + b * ldx (bf16, K elements),
+ * W8 [N or 2N, K] fp8 e4m3 with one fp32 scale per weight row, y[b] = y + b * ldy (out_dtype VG_BF16 | VG_F32), residual R + b * ldr of the output
+ * dtype, norm_w / eps and glu as vg_decode_gemv_w8.  Row b is bit-identical to vg_decode_gemv_w8 on row b alone; every weight chunk is read once.
+ * B in [1, 16], staged in buckets of 1, 2, 4, 8, 16 rows; K must be one of 3072, 4096, 8192, 14336 (vg_decode_gemv_w8_rows_supported(K) != 0);
+ * x, W8 and norm_w 16-byte aligned, ldx a multiple of 8, ldw of 16.  LDS: without a norm the rows are staged in phases of at most 64 KiB; with a
+ * norm the whole rows of the bucket are staged, so bucket x K x 2 bytes must fit 152 KiB (K <= 4096 at 16 rows), VG_ERR_UNSUPPORTED otherwise. */
+int vg_decode_gemv_w8_rows_supported(int K);
+int vg_decode_gemv_w8_rows(const void* x, int64_t ldx, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, int64_t ldy,
+                           const float* norm_w, float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype,
+                           vg_stream_t stream);
 int vg_decode_qkv_rope_rows(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, int64_t ldq,
                             void* k_slots, void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* rope_cs, const int* pos,
                             int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream);

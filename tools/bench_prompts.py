@@ -8,10 +8,12 @@ differ in their 30 question ids.  One JSON line per LLM:
   "ratio"[B]:         prompts_ms / sequential_ms
   "decode_step_ms":   one replayed decode step of one prompt (LlamaDecoder.decode_step, the step the sequential loop decodes with), ms per token
   "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode: Llama-3 and Phi-3-mini widths), ms per step
+--decode-weights fp8 / --prefill fp8: the fp8 LLM path (bench.py's switches of the same names), written into each line.
 --ab also times inference_prompts() with VG_PROMPTS_BATCHED=0 ("prompts_seq_ms"[B]: the prompts decoded one after another).
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 
-    python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise] [--ab] [--out FILE]
+    python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise]
+                                   [--decode-weights fp8] [--prefill fp8] [--ab] [--out FILE]
 """
 import argparse
 import json
@@ -78,6 +80,10 @@ def rows_step_ms(model, tokens=32):
 def run(llm, args, device):
     cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
+    if args.decode_weights == "fp8":
+        cfg["llm"] = dict(cfg["llm"], decode_weights="fp8")
+    if args.prefill == "fp8":
+        cfg["llm"] = dict(cfg["llm"], prefill_gemm="fp8")
     sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
     model = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, cfg, torch_dtype=torch.bfloat16, device=device))
     g = torch.Generator().manual_seed(1234)
@@ -90,7 +96,8 @@ def run(llm, args, device):
     prompts = [torch.cat([head, torch.randint(3, cfg["llm"]["vocab"] - 2, (30,), generator=g)]) for _ in range(max(args.batches))]
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
-    rec = dict(llm=llm, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, prompts_ms={}, sequential_ms={}, ratio={},
+    rec = dict(llm=llm, decode_weights=args.decode_weights, prefill=args.prefill, branch=args.branch, frames=args.frames,
+               max_new_tokens=args.max_new_tokens, prompts_ms={}, sequential_ms={}, ratio={},
                rows_step_ms={})
     if args.ab:
         rec["prompts_seq_ms"] = {}
@@ -123,6 +130,9 @@ def main():
     ap.add_argument("--src", type=int, default=1024)
     ap.add_argument("--max-new-tokens", type=int, default=32)
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
+    ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: the decode step's MLP and lm_head weights in fp8 (e4m3, row scales), as bench.py --decode-weights")
+    ap.add_argument("--prefill", default="bf16", choices=["bf16", "fp8"], help="fp8: the LLM prefill GEMMs on the fp8 MFMA path, as bench.py --prefill")
     ap.add_argument("--ab", action="store_true", help="also time inference_prompts() on the sequential loop (VG_PROMPTS_BATCHED=0)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()

@@ -1,5 +1,7 @@
 """Kernel-trace driver of the batched decode step: 8 prompts through prompts.generate_prompts at full Phi-3-mini width (32 layers, bf16 synthetic weights), prefix P = 1700 rows,
-then 24 replayed B = 8 batched steps (the dispatches a kernel trace then cuts out: the last 24 steps)."""
+then 24 replayed B = 8 batched steps (the dispatches a kernel trace then cuts out: the last 24 steps).
+--decode-weights fp8: the step with fp8 decode weights (the MLP and the lm_head on vg_decode_gemv_w8_rows)."""
+import argparse
 import os
 import sys
 import time
@@ -11,6 +13,9 @@ from videoglamm_amd import synth  # noqa: E402
 from videoglamm_amd.params import Params  # noqa: E402
 from videoglamm_amd.prompts import generate_prompts  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"])
+args = ap.parse_args()
 torch.set_grad_enabled(False)
 
 
@@ -27,7 +32,7 @@ full = synth.videoglamm_phi3_mini()
 man = {k: v for k, v in synth.vlm_manifest(full).items()
        if k.startswith(("model.layers.", "model.norm", "model.embed_tokens", "lm_head", "model.text_hidden_fcs"))}
 P = Params(synth.device_state_dict(man, dev, torch.bfloat16), dev, torch.bfloat16)
-c = full["llm"]
+c = full["llm"] if args.decode_weights == "bf16" else dict(full["llm"], decode_weights="fp8")
 g = torch.Generator().manual_seed(1)
 nvis = 1697
 visual = (torch.randn(nvis, c["hidden"], generator=g) * 0.5).to(torch.bfloat16).to(dev)

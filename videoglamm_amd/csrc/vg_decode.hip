@@ -751,6 +751,214 @@ extern "C" int vg_decode_qkv_rope_rows(const void* x, int64_t ldx, const void* W
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// B-row form of vg_decode_gemv_w8 (fp8 e4m3 weights with per-row scales; the MLP and the lm_head of the batched step with fp8 decode weights,
+// DESIGN 11): every weight chunk is loaded once and applied to the BR rows of x, and row r of the result is bit-identical to vg_decode_gemv_w8 on
+// row r alone.  The single-row kernel walks a weight row as the flat sequence of 64-chunk steps s = cb * CPB + u (weight chunk wc = 64 s + lane
+// against the x chunks 2 wc and 2 wc + 1), one fp32 accumulator per pair row fed dec_dot_w8 in that order — so only the ORDER of the steps enters
+// the sums, and how they are grouped into load batches is free (launch_w8_rows_k picks two chunks per lane per batch where the single-row kernel
+// has four).  The norm prologue is decode_gemv_fast_kernel's for that K (256 threads, the same x chunks per thread, wave sums, the 4-wave total, dec_round before the norm weight), the scale and the epilogue are
+// dec_gemv_store's.  x is staged as bf16 rows with the even and the odd x chunks of a row in two planes ([BR][2][chunks]: a lane's two 16-byte
+// reads per weight chunk are then 16 bytes apart from its neighbours' instead of 32); phases as in decode_gemv_rows_kernel when B x K x 2 bytes
+// exceed the budget and there is no norm.
+struct DecRowsW8Args {
+  const void* x; int64_t ldx; const uint8_t* W; int64_t ldw; const float* wscale; void* y; int64_t ldy; const float* nw; float eps;
+  const void* R; int64_t ldr; int N, K, B, ppw, nph;
+};
+
+template <typename TO, bool GLU, int NB, int CPB, int BR>
+__global__ __launch_bounds__(256) void decode_gemv_w8_rows_kernel(DecRowsW8Args p) {
+  typedef bf16_t T;
+  constexpr int KPC = 8, NWV = 2;
+  constexpr int BC = CPB * 64;                     // WEIGHT chunks per batch (16 K elements each = two x chunks)
+  constexpr int NCH = NB * BC * 2, XN = (NCH + 255) / 256;     // x chunks per row; the last one per thread may be partial (K = 3072)
+  extern __shared__ __attribute__((aligned(16))) char dec_smem[];
+  __shared__ float red[BR][4];
+  __shared__ float res[4][DEC_ROWS_PPW][BR][2];
+  u32x4_t* xs = (u32x4_t*)dec_smem;                // [BR][2][nph * BC]: x chunk 2 wc + h of the phase at plane h, index wc
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int npair = GLU ? p.N : (p.N + 1) / 2;
+  const int p0 = (blockIdx.x * 4 + wave) * p.ppw;
+  const int np = max(min(p0 + p.ppw, npair) - p0, 0);
+  const uint8_t* W = p.W;
+  const int pch = p.nph * BC;                      // weight chunks per row per phase
+
+  float rstd[BR];
+#pragma unroll
+  for (int r = 0; r < BR; ++r) rstd[r] = 1.f;
+  if (p.nw) {                                      // the launcher keeps nph = NB with a norm (whole rows)
+#pragma unroll
+    for (int r = 0; r < BR; ++r) {
+      const u32x4_t* xg = (const u32x4_t*)((const T*)p.x + (int64_t)min(r, p.B - 1) * p.ldx);
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < XN; ++i) {
+        if (NCH % 256 == 0 || tid + 256 * i < NCH) {
+          float f[KPC];
+          dec_unpack<T>(xg[tid + 256 * i], f);
+#pragma unroll
+          for (int e = 0; e < KPC; ++e) ss += f[e] * f[e];
+        }
+      }
+      ss = wave_sum(ss);
+      if (lane == 0) red[r][wave] = ss;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < BR; ++r) rstd[r] = rsqrtf((red[r][0] + red[r][1] + red[r][2] + red[r][3]) / (float)p.K + p.eps);
+  }
+
+  float a0[BR], a1[BR];
+#pragma unroll
+  for (int r = 0; r < BR; ++r) { a0[r] = 0.f; a1[r] = 0.f; }
+  for (int ph = 0; ph < NB; ph += p.nph) {
+    const int nbp = min(p.nph, NB - ph);
+    if (ph > 0) __syncthreads();                   // every wave is done with the previous phase's rows
+    // ---- stage the rows' x chunks [2 ph BC, 2 (ph + nbp) BC)
+    for (int c = tid; c < nbp * BC * 2; c += 256) {
+      const int gc = ph * BC * 2 + c;
+#pragma unroll
+      for (int r = 0; r < BR; ++r) {
+        u32x4_t v = ((const u32x4_t*)((const T*)p.x + (int64_t)min(r, p.B - 1) * p.ldx))[gc];
+        if (p.nw) {
+          float f[KPC];
+          dec_unpack<T>(v, f);
+          const f32x4_t* nw4 = (const f32x4_t*)p.nw + gc * NWV;
+#pragma unroll
+          for (int e = 0; e < KPC; ++e) f[e] = dec_round<T>(f[e] * rstd[r]) * nw4[e / 4][e % 4];
+          v = dec_pack<T>(f);
+        }
+        xs[(2 * r + (c & 1)) * pch + (c >> 1)] = v;
+      }
+    }
+    __syncthreads();
+    // ---- the stream: flat (pair, batch-of-phase) sequence, two batches in flight
+    const int total = np * nbp;
+    auto issue = [&](u32x4_t (&v0)[CPB], u32x4_t (&v1)[CPB], int it) {
+      const int pc = p0 + it / nbp, cb = ph + it % nbp;
+      const int n0 = GLU ? pc : 2 * pc;
+      const int n1 = GLU ? p.N + pc : min(2 * pc + 1, p.N - 1);
+      const u32x4_t* w0 = (const u32x4_t*)(W + (int64_t)n0 * p.ldw) + cb * BC + lane;
+      const u32x4_t* w1 = (const u32x4_t*)(W + (int64_t)n1 * p.ldw) + cb * BC + lane;
+#pragma unroll
+      for (int u = 0; u < CPB; ++u) {
+        v0[u] = __builtin_nontemporal_load(w0 + u * 64);
+        v1[u] = __builtin_nontemporal_load(w1 + u * 64);
+      }
+    };
+    auto consume = [&](const u32x4_t (&v0)[CPB], const u32x4_t (&v1)[CPB], int it) {
+      const int li = it / nbp, cbl = it % nbp;
+#pragma unroll
+      for (int r = 0; r < BR; ++r) {               // row-outer: one row's x chunks live at a time; each row's sum order is the single-row one
+#pragma unroll
+        for (int u = 0; u < CPB; ++u) {
+          const int wcl = cbl * BC + u * 64 + lane;
+          const u32x4_t xa = xs[(2 * r) * pch + wcl], xb = xs[(2 * r + 1) * pch + wcl];
+          a0[r] += dec_dot_w8(v0[u], xa, xb);
+          a1[r] += dec_dot_w8(v1[u], xa, xb);
+        }
+      }
+      if (cbl == nbp - 1 && ph + nbp == NB) {      // the pair's last batch
+#pragma unroll
+        for (int r = 0; r < BR; ++r) {
+          const float s0 = wave_sum(a0[r]), s1 = wave_sum(a1[r]);
+          if (lane == 0) { res[wave][li][r][0] = s0; res[wave][li][r][1] = s1; }
+          a0[r] = 0.f;
+          a1[r] = 0.f;
+        }
+      }
+    };
+    u32x4_t va0[CPB], va1[CPB], vb0[CPB], vb1[CPB];
+    if (total > 0) issue(va0, va1, 0);
+    if (total > 1) issue(vb0, vb1, 1);
+    int it = 0;
+    for (; it + 1 < total; it += 2) {
+      consume(va0, va1, it);
+      if (it + 2 < total) issue(va0, va1, it + 2);
+      consume(vb0, vb1, it + 1);
+      if (it + 3 < total) issue(vb0, vb1, it + 3);
+    }
+    if (it < total) consume(va0, va1, it);
+  }
+  // ---- epilogue: one lane per (pair, row); the single-row kernel's scale and stores
+  for (int i = lane; i < np * BR; i += 64) {
+    const int li = i / BR, r = i % BR;
+    if (r >= p.B) continue;
+    DecGemvArgs q{};
+    q.y = (TO*)p.y + r * p.ldy;
+    q.R = p.R ? (const void*)((const TO*)p.R + r * p.ldr) : nullptr;
+    q.N = p.N;
+    q.wscale = p.wscale;
+    dec_gemv_store<T, TO, GLU>(q, p0 + li, res[wave][li][r][0], res[wave][li][r][1]);
+  }
+}
+
+// the row lengths of vg_decode_gemv_w8's fast walk
+extern "C" int vg_decode_gemv_w8_rows_supported(int K) { return K == 3072 || K == 4096 || K == 8192 || K == 14336; }
+
+template <typename TO, bool GLU, int NB, int CPB, int BR>
+static int launch_w8_rows_b(DecRowsW8Args p, hipStream_t st) {
+  const int npair = GLU ? p.N : (p.N + 1) / 2;
+  constexpr int BBYTES = CPB * 64 * 32;            // bytes of x under one row's batch of weight chunks
+  // x staging: the whole row when it fits the budget (always with the norm), else phases of batches with one pair per wave
+  int nph = NB;
+  if (!p.nw && (int64_t)BR * NB * BBYTES > DEC_ROWS_LDS) nph = max(1, DEC_ROWS_LDS / (BR * BBYTES));
+  int ppw = (npair + 2047) / 2048;                  // ~2 workgroups per CU, as vg_decode_gemv_rows
+  ppw = nph < NB ? 1 : min(ppw, DEC_ROWS_PPW);
+  p.nph = nph;
+  p.ppw = ppw;
+  const size_t lds = (size_t)BR * nph * BBYTES;
+  static size_t cap = 64 * 1024;
+  if (lds > 64 * 1024 && lds > cap) {
+    (void)hipFuncSetAttribute((const void*)decode_gemv_w8_rows_kernel<TO, GLU, NB, CPB, BR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    cap = lds;
+  }
+  decode_gemv_w8_rows_kernel<TO, GLU, NB, CPB, BR><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+// Load batches per K: vg_decode_gemv_w8's (3, 1) and (7, 2) at K = 3072 and 14336; its batches of four chunks per lane at K = 4096 and 8192 are
+// split in two — (2, 2) and (4, 2): the same steps in the same order, so every sum keeps its bits — because the fp8 -> fp32 conversions of a batch
+// are shared by the B rows and four chunks of two weight rows converted (128 registers) leave no room for the rows' accumulators, and because one
+// batch of a 16-row bucket then fits the staging budget
+template <typename TO, bool GLU, int BR>
+static int launch_w8_rows_k(DecRowsW8Args p, hipStream_t st) {
+  switch (p.K) {
+    case 3072: return launch_w8_rows_b<TO, GLU, 3, 1, BR>(p, st);
+    case 4096: return launch_w8_rows_b<TO, GLU, 2, 2, BR>(p, st);
+    case 8192: return launch_w8_rows_b<TO, GLU, 4, 2, BR>(p, st);
+    default: return launch_w8_rows_b<TO, GLU, 7, 2, BR>(p, st);
+  }
+}
+
+template <typename TO, bool GLU>
+static int launch_w8_rows(DecRowsW8Args p, hipStream_t st) {
+  if (p.B <= 1) return launch_w8_rows_k<TO, GLU, 1>(p, st);
+  if (p.B <= 2) return launch_w8_rows_k<TO, GLU, 2>(p, st);
+  if (p.B <= 4) return launch_w8_rows_k<TO, GLU, 4>(p, st);
+  if (p.B <= 8) return launch_w8_rows_k<TO, GLU, 8>(p, st);
+  return launch_w8_rows_k<TO, GLU, 16>(p, st);
+}
+
+extern "C" int vg_decode_gemv_w8_rows(const void* x, int64_t ldx, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, int64_t ldy,
+                                      const float* norm_w, float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype,
+                                      vg_stream_t stream) {
+  VG_CHECK(x && W8 && wscale && y && N > 0 && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemv_w8_rows: bad args N=%d B=%d", N, B);
+  VG_CHECK(vg_decode_gemv_w8_rows_supported(K), VG_ERR_UNSUPPORTED,
+           "vg_decode_gemv_w8_rows: K=%d is not one of the supported row lengths (3072, 4096, 8192, 14336)", K);
+  VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemv_w8_rows: bad out_dtype %d", out_dtype);
+  VG_CHECK(ldw % 16 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)W8) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
+           "vg_decode_gemv_w8_rows: alignment (16 bytes; ldx a multiple of 8, ldw of 16)");
+  const int br = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;      // the bucket the kernel stages
+  VG_CHECK(!norm_w || (int64_t)br * K * 2 <= 160 * 1024 - 8 * 1024, VG_ERR_UNSUPPORTED,
+           "vg_decode_gemv_w8_rows: the norm stages the whole rows of the %d-row bucket: B=%d K=%d do not fit", br, B, K);
+  DecRowsW8Args p{x, ldx, W8, ldw, wscale, y, ldy, norm_w, eps, R, ldr, N, K, B, 1, 1};
+  hipStream_t st = (hipStream_t)stream;
+  if (out_dtype == VG_BF16) return glu ? launch_w8_rows<bf16_t, true>(p, st) : launch_w8_rows<bf16_t, false>(p, st);
+  return glu ? launch_w8_rows<float, true>(p, st) : launch_w8_rows<float, false>(p, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Attention of the one new token.  grid = (ceil(max_len/64) splits, Hkv): a workgroup owns 64 keys of one KV head and
 // the G = H/Hkv query heads that share it.  All K and V bytes of the split are requested up front (one HBM round
 // trip), RoPE of q and of the new k runs while they are in flight, the workgroup that owns position `pos` appends the

@@ -827,6 +827,31 @@ def decode_gemv_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out=N
     return y
 
 
+def decode_gemv_w8_rows_supported(K):
+    """True when the B-row fp8 GEMV has the row length K (vg_decode_gemv_w8_rows_supported: 3072, 4096, 8192, 14336)."""
+    return bool(_lib.load().vg_decode_gemv_w8_rows_supported(int(K)))
+
+
+def decode_gemv_w8_rows(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """decode_gemv_w8 on each of the B rows of x [B,K] (vg_decode_gemv_w8_rows): one pass over the fp8 weights for all rows -> [B,N]."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w8.dtype == torch.uint8 and w8.stride(1) == 1 and w8.shape[1] == K
+    assert wscale.dtype == torch.float32 and wscale.numel() == w8.shape[0] and wscale.is_contiguous()
+    N = w8.shape[0] // 2 if glu else w8.shape[0]
+    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
+    assert y.shape == (B, N) and y.stride(1) == 1
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
+        ldr = residual.stride(0)
+    rc = lib.vg_decode_gemv_w8_rows(_p(x), x.stride(0), _p(w8), w8.stride(0), _p(wscale), _p(y), y.stride(0),
+                                    _p(None if norm_w is None else _f32(norm_w)), float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y),
+                                    _stream())
+    _lib.check(rc, "vg_decode_gemv_w8_rows")
+    return y
+
+
 def decode_qkv_rope_rows(x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out=None):
     """decode_qkv_rope on each row of x [B,K]: row b at position pos_dev[b] with rope_cs[b], its K / V rows into slot b of k_slots / v_slots
     ([B, rows, Hkv, D], row j of the sequence at j - row0) -> rotated q [B, H*D]."""

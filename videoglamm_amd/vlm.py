@@ -576,11 +576,22 @@ class RowsDecode:
                 o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
                                                d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
             x = ops.decode_gemv_rows(o, P.w(l + "self_attn.o_proj"), residual=x)
-            wgu, _ = P.fused([l + "mlp.gate_proj", l + "mlp.up_proj"], stored=l + "mlp.gate_up_proj")
-            a = ops.decode_gemv_rows(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
-            x = ops.decode_gemv_rows(a, P.w(l + "mlp.down_proj"), residual=x)
+            gu_names = [l + "mlp.gate_proj", l + "mlp.up_proj"]
+            if d.w8:
+                # fp8 decode weights: the MLP and (below) the lm_head on the B-row fp8 GEMV, the operands LlamaDecoder._layers_decode picks; the
+                # attention projections stay bf16 as they do there
+                a = ops.decode_gemv_w8_rows(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                                            eps=c["rms_eps"], glu=True)
+                x = ops.decode_gemv_w8_rows(a, *P.fp8(l + "mlp.down_proj"), residual=x)
+            else:
+                wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
+                a = ops.decode_gemv_rows(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
+                x = ops.decode_gemv_rows(a, P.w(l + "mlp.down_proj"), residual=x)
         h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
-        logits = ops.linear(h, P.w("lm_head"), out_dtype=torch.float32)
+        if d.w8:
+            logits = ops.decode_gemv_w8_rows(h, *P.fp8("lm_head"), out_dtype=torch.float32)
+        else:
+            logits = ops.linear(h, P.w("lm_head"), out_dtype=torch.float32)
         if self.route == "greedy":
             ops.argmax_partial_rows(logits, self.acc)
         else:

@@ -452,6 +452,19 @@ int vg_upsample2_add(const void* lateral, const void* top, void* y, int B, int H
  * K in {3072, 4096, 8192, 14336}. */
 int vg_decode_gemv_w8(const void* x, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, const float* norm_w,
                       float eps, const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream);
+/* vg_decode_gemv with MXFP4 weights (OCP Microscaling v1.0; cfg decode_weights = "mxfp4", the MLP of the decode step — weight-only
+ * quantisation of what R/chat.py:247-272 asks of bitsandbytes' load_in_4bit, in gfx950's own 4-bit format): blocks of 32 consecutive K elements of
+ * a weight row share the scale 2^(s - 127) (one e8m0 byte s), the elements are e2m1 codes (bit 3 sign; magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6), element
+ * 2j in the low nibble of byte j.  y[n] = sum_k 2^(s[n, k / 32] - 127) * e2m1(W4[n, k]) * xn[k]: each code is converted to bf16 with its scale
+ * applied (exact), multiplied with the bf16 activation and summed in fp32; x, the norm, glu, R and the epilogue as vg_decode_gemv_w8.
+ * K in {3072, 4096, 8192, 14336}, VG_ERR_UNSUPPORTED otherwise.  A block with s = 0 counts as zero.  Two layouts:
+ *   scales != NULL: W4 row n = K / 2 code bytes at W4 + n * ldw_bytes; scales [rows, K / 32] contiguous, block b of row n at scales[n * K / 32 + b].
+ *   scales == NULL (packed rows, the decoder's form): row n at W4 + n * ldw_bytes = a head of 64 * SPL scale bytes, then the K / 2 code bytes;
+ *     SPL = 2 (K = 3072, 4096), 4 (8192), 8 (14336); head byte lane * SPL + u = the scale of block 64 u + lane (0 where K / 32 <= 64 u + lane):
+ *     the scales one lane needs are one 2 / 4 / 8-byte load.
+ * ldw_bytes a multiple of 16 that covers the row; x, W4, norm_w 16-byte aligned. */
+int vg_decode_gemv_w4(const void* x, const uint8_t* W4, int64_t ldw_bytes, const uint8_t* scales, void* y, const float* norm_w, float eps,
+                      const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream);
 /* vg_gemm for grids that leave most of the chip idle (few 128x128 tiles, long K): K is cut into ksplit slices that run as
  * separate workgroups, the fp32 partial tiles go to `workspace` (>= ksplit*M*N floats) and one pass sums them and applies
  * bias / act / gamma / residual.  Same result up to fp32 summation order.  M > 16, N % 8 == 0, no batch / GLU / window. */

@@ -13,7 +13,7 @@ differ in their 30 question ids.  One JSON line per LLM:
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 
     python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise]
-                                   [--decode-weights fp8] [--prefill fp8] [--ab] [--out FILE]
+                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--ab] [--out FILE]
 """
 import argparse
 import json
@@ -80,8 +80,8 @@ def rows_step_ms(model, tokens=32):
 def run(llm, args, device):
     cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
-    if args.decode_weights == "fp8":
-        cfg["llm"] = dict(cfg["llm"], decode_weights="fp8")
+    if args.decode_weights in ("fp8", "mxfp4"):
+        cfg["llm"] = dict(cfg["llm"], decode_weights=args.decode_weights)
     if args.prefill == "fp8":
         cfg["llm"] = dict(cfg["llm"], prefill_gemm="fp8")
     sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
@@ -130,8 +130,9 @@ def main():
     ap.add_argument("--src", type=int, default=1024)
     ap.add_argument("--max-new-tokens", type=int, default=32)
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
-    ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"],
-                    help="fp8: the decode step's MLP and lm_head weights in fp8 (e4m3, row scales), as bench.py --decode-weights")
+    ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+                    help="fp8: the decode step's MLP and lm_head weights in fp8 (e4m3, row scales), as bench.py --decode-weights; mxfp4: the MLP in MXFP4, "
+                         "the lm_head in fp8 (inference_prompts() runs such a model's prompts as one inference() each: there is no B-row MXFP4 GEMV)")
     ap.add_argument("--prefill", default="bf16", choices=["bf16", "fp8"], help="fp8: the LLM prefill GEMMs on the fp8 MFMA path, as bench.py --prefill")
     ap.add_argument("--ab", action="store_true", help="also time inference_prompts() on the sequential loop (VG_PROMPTS_BATCHED=0)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")

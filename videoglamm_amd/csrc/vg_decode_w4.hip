@@ -1,0 +1,274 @@
+// Decode-step GEMV with MXFP4 weights (OCP Microscaling v1.0: e2m1 elements, one e8m0 scale per 32 consecutive K elements of a weight row):
+// vg_decode_gemv_w4, the 4-bit sibling of vg_decode_gemv_w8 (vg_decode.hip).  The structure is decode_gemv_fast_kernel's — x staged once per workgroup
+// in LDS (normalised on the way), row PAIRS per wave, every weight load of a pair issued before its first use and two pairs in flight (one at K = 14336), wave_sum on the
+// VALU, results parked in LDS and written by a lane-per-pair epilogue — with the row walk cut to the format:
+//   * a lane's 16-byte load is 32 codes = exactly one scale block, so a whole row is CPL = K / 2048 loads per lane (2, 2, 4, 7 at K = 3072 (the second
+//     one on half the lanes), 4096, 8192, 14336) and ONE batch: a pair is 2 x CPL loads, reduced once;
+//   * v_cvt_scalef32_pk_bf16_fp4 turns a byte (two codes) into two bf16 with the block scale applied (exact: two significant bits times a power of
+//     two), v_dot2c_f32_bf16 multiplies them with the staged bf16 x pair and accumulates in fp32: one instruction per weight;
+//   * x sits in LDS in four planes (x chunk 4 c + h of weight chunk c at plane h, index c): the four 16-byte reads a lane makes per weight chunk are
+//     then 16 bytes apart from its neighbours' instead of 64 (no bank conflicts).
+// The scale bytes are 1/16 of the code bytes and come one of two ways (vg_kernels.h): a head of 64 x SPL bytes in front of every row's codes, ordered so
+// that a lane's SPL scales are ONE 2 / 4 / 8-byte load (packed rows, scales == NULL), or a second array in the logical order read with one byte load per
+// chunk (the 64 lanes of a wave cover one 64-byte line).
+#include "vg_common.h"
+#include <type_traits>
+
+struct DecW4Args {
+  const void* x; const uint8_t* W; const uint8_t* sc; void* y; const float* nw; const void* R;
+  int N, K; int64_t ldw; float eps; int ppw;
+};
+
+constexpr int DEC4_MAX_PPW = 64;
+
+// the epilogue of dec_gemv_store (vg_decode.hip) for bf16 activations: gate / up materialise in bf16, silu rounded to bf16, residual in the output dtype
+template <typename TO, bool GLU>
+__device__ __forceinline__ void dec4_store(const DecW4Args& p, int pi, float a0, float a1) {
+  const int n0 = GLU ? pi : 2 * pi, n1 = GLU ? p.N + pi : 2 * pi + 1;
+  TO* y = (TO*)p.y;
+  const TO* R = (const TO*)p.R;
+  if constexpr (GLU) {
+    const float g = bf2f(f2bf(vg_silu(bf2f(f2bf(a0))))), u = bf2f(f2bf(a1));
+    float v = g * u;
+    if (R) v += vg_elt<TO>::ld(R + n0);
+    vg_elt<TO>::st(y + n0, v);
+  } else {
+    float v = a0;
+    if (R) v += vg_elt<TO>::ld(R + n0);
+    vg_elt<TO>::st(y + n0, v);
+    if (n1 < p.N) {
+      v = a1;
+      if (R) v += vg_elt<TO>::ld(R + n1);
+      vg_elt<TO>::st(y + n1, v);
+    }
+  }
+}
+
+// e8m0 scale byte -> the float 2^(b - 127) (b = 0 gives 0.0f, not 2^-127: a block that small contributes nothing)
+__device__ __forceinline__ float dec4_scale(uint32_t b) { return __uint_as_float(b << 23); }
+
+// a dword of two bf16 as the dot instruction's operand type (by value: a bit cast applied to a vector ELEMENT reads element 0 of the vector)
+__device__ __forceinline__ vg_bf16x2_t dec4_bf2(uint32_t v) { return __builtin_bit_cast(vg_bf16x2_t, v); }
+
+// 32 e2m1 codes of one chunk (element 2j in the low nibble of byte j) times the block scale against the 32 bf16 of four x chunks
+__device__ __forceinline__ float dec4_dot(const u32x4_t& w, float sc, const u32x4_t (&x)[4], float s) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const uint32_t we = w[e], x0 = x[e][0], x1 = x[e][1], x2 = x[e][2], x3 = x[e][3];
+    s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(we, sc, 0), dec4_bf2(x0), s, false);
+    s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(we, sc, 1), dec4_bf2(x1), s, false);
+    s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(we, sc, 2), dec4_bf2(x2), s, false);
+    s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(we, sc, 3), dec4_bf2(x3), s, false);
+  }
+  return s;
+}
+
+// NWC = K / 32 weight chunks per row (96, 128, 256, 448), CPL = ceil(NWC / 64) per lane, SPL = scale bytes per lane in a packed row's head (CPL rounded
+// up to 2, 4 or 8).  SEP: the scales are a second array [rows, NWC] (p.sc) instead of the row heads.
+template <int NWC> struct Dec4Shape {
+  static constexpr int CPL = (NWC + 63) / 64;
+  static constexpr int SPL = CPL <= 2 ? 2 : CPL <= 4 ? 4 : 8;
+  typedef typename std::conditional<SPL == 2, uint16_t, typename std::conditional<SPL == 4, uint32_t, uint64_t>::type>::type sc_t;
+};
+
+template <typename TO, bool GLU, int NWC, bool SEP>
+__global__ __launch_bounds__(256) void decode_gemv_w4_kernel(DecW4Args p) {
+  typedef Dec4Shape<NWC> S;
+  constexpr int CPL = S::CPL, SPL = S::SPL;
+  constexpr bool PART = NWC % 64 != 0;            // the last chunk per lane exists on the low lanes only (K = 3072)
+  constexpr int NCH = NWC * 4;                    // 16-byte chunks of x
+  constexpr int XN = (NCH + 255) / 256;
+  typedef typename S::sc_t sc_t;
+  extern __shared__ __attribute__((aligned(16))) char dec4_smem[];
+  __shared__ float red[4];
+  __shared__ float res[4][DEC4_MAX_PPW][2];
+  u32x4_t* xs = (u32x4_t*)dec4_smem;               // [4][NWC]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int npair = GLU ? p.N : (p.N + 1) / 2;
+  const int p0 = (blockIdx.x * 4 + wave) * p.ppw;
+  const int np = max(min(p0 + p.ppw, npair) - p0, 0);     // pairs of this wave
+
+  // ---- 1. every load up front, oldest-needed first: x, the norm weights, two pairs of W
+  u32x4_t xr[XN];
+#pragma unroll
+  for (int i = 0; i < XN; ++i) xr[i] = ((const u32x4_t*)p.x)[min(tid + 256 * i, NCH - 1)];
+  f32x4_t nwr[XN][2];
+  if (p.nw) {
+#pragma unroll
+    for (int i = 0; i < XN; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) nwr[i][j] = ((const f32x4_t*)p.nw)[min(tid + 256 * i, NCH - 1) * 2 + j];
+  }
+  struct Set { u32x4_t v0[CPL], v1[CPL]; sc_t s0, s1; uint8_t b0[SEP ? CPL : 1], b1[SEP ? CPL : 1]; };
+  int ipi = p0;                    // issue cursor
+  auto issue = [&](Set& t) {
+    const int pc = min(ipi, npair - 1);                       // clamped: the two prologue issues are unconditional
+    const int n0 = GLU ? pc : 2 * pc, n1 = GLU ? p.N + pc : min(2 * pc + 1, p.N - 1);
+    const uint8_t* r0 = p.W + (int64_t)n0 * p.ldw;
+    const uint8_t* r1 = p.W + (int64_t)n1 * p.ldw;
+    if constexpr (SEP) {
+#pragma unroll
+      for (int u = 0; u < CPL; ++u) {
+        const int c = min(u * 64 + lane, NWC - 1);
+        t.b0[u] = __builtin_nontemporal_load(p.sc + (int64_t)n0 * NWC + c);
+        t.b1[u] = __builtin_nontemporal_load(p.sc + (int64_t)n1 * NWC + c);
+      }
+    } else {
+      t.s0 = __builtin_nontemporal_load((const sc_t*)r0 + lane);
+      t.s1 = __builtin_nontemporal_load((const sc_t*)r1 + lane);
+      r0 += 64 * SPL;
+      r1 += 64 * SPL;
+    }
+#pragma unroll
+    for (int u = 0; u < CPL; ++u) {
+      const int c = PART ? min(u * 64 + lane, NWC - 1) : u * 64 + lane;
+      t.v0[u] = __builtin_nontemporal_load((const u32x4_t*)r0 + c);
+      t.v1[u] = __builtin_nontemporal_load((const u32x4_t*)r1 + c);
+    }
+    ++ipi;
+  };
+  // two pairs in flight per wave; K = 14336 (14 loads = 56 registers per pair) keeps one and leaves the overlap to the other waves of the CU: a second
+  // set would not fit 256 registers.  A wave's first pair is clamped, so a wave without pairs loads (and drops) the last one.
+  constexpr bool TWO = CPL <= 4;
+  Set sa, sb;
+  issue(sa);
+  if (TWO && np > 1) issue(sb);
+
+  // ---- 2. stage x (normalised, the arithmetic of decode_gemv_fast_kernel) into the four LDS planes
+  {
+    float rstd = 1.f;
+    if (p.nw) {
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < XN; ++i) {
+        if (tid + 256 * i < NCH) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float lo = __uint_as_float(xr[i][e] << 16), hi = __uint_as_float(xr[i][e] & 0xffff0000u);
+            ss += lo * lo;
+            ss += hi * hi;
+          }
+        }
+      }
+      ss = wave_sum(ss);
+      if (lane == 0) red[wave] = ss;
+      __syncthreads();
+      rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)p.K + p.eps);
+#pragma unroll
+      for (int i = 0; i < XN; ++i) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float lo = __uint_as_float(xr[i][e] << 16), hi = __uint_as_float(xr[i][e] & 0xffff0000u);
+          xr[i][e] = f2bf2(bf2f(f2bf(lo * rstd)) * nwr[i][e / 2][2 * (e % 2)], bf2f(f2bf(hi * rstd)) * nwr[i][e / 2][2 * (e % 2) + 1]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < XN; ++i) {
+      const int c = tid + 256 * i;
+      if (c < NCH) xs[(c & 3) * NWC + (c >> 2)] = xr[i];
+    }
+    __syncthreads();
+  }
+
+  // ---- 3. the stream: no stores inside (a pending store makes every later vmcnt wait a full drain), results to LDS
+  int cpl = 0;
+  auto consume = [&](const Set& t) {
+    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int u = 0; u < CPL; ++u) {
+      const int c = u * 64 + lane;
+      const int cx = PART ? min(c, NWC - 1) : c;
+      const u32x4_t xv[4] = {xs[cx], xs[NWC + cx], xs[2 * NWC + cx], xs[3 * NWC + cx]};
+      u32x4_t w0 = t.v0[u], w1 = t.v1[u];
+      if (PART && u == CPL - 1 && c >= NWC) {      // no such chunk: +0 codes
+        w0 = u32x4_t{0, 0, 0, 0};
+        w1 = u32x4_t{0, 0, 0, 0};
+      }
+      const uint32_t e0 = SEP ? (uint32_t)t.b0[u] : (uint32_t)(t.s0 >> (8 * u)) & 0xffu;
+      const uint32_t e1 = SEP ? (uint32_t)t.b1[u] : (uint32_t)(t.s1 >> (8 * u)) & 0xffu;
+      a0 = dec4_dot(w0, dec4_scale(e0), xv, a0);
+      a1 = dec4_dot(w1, dec4_scale(e1), xv, a1);
+    }
+    a0 = wave_sum(a0);
+    a1 = wave_sum(a1);
+    if (lane == 0) { res[wave][cpl][0] = a0; res[wave][cpl][1] = a1; }
+    ++cpl;
+  };
+  if constexpr (TWO) {
+    int b = 0;
+    for (; b + 4 <= np; b += 2) {      // on entry: pair b in set a, pair b+1 in set b
+      consume(sa);
+      issue(sa);
+      consume(sb);
+      issue(sb);
+    }
+    const int rem = np - b;
+    if (rem == 3) {
+      consume(sa);
+      issue(sa);
+      consume(sb);
+      consume(sa);
+    } else if (rem == 2) {
+      consume(sa);
+      consume(sb);
+    } else if (rem == 1) {
+      consume(sa);
+    }
+  } else {
+    for (int b = 0; b < np; ++b) {
+      consume(sa);
+      if (b + 1 < np) issue(sa);
+    }
+  }
+  // ---- 4. epilogue: one lane per pair
+  for (int i = lane; i < np; i += 64) dec4_store<TO, GLU>(p, p0 + i, res[wave][i][0], res[wave][i][1]);
+}
+
+static int dec4_spl(int K) { return K == 3072 || K == 4096 ? 2 : K == 8192 ? 4 : K == 14336 ? 8 : 0; }
+
+static int64_t dec4_row_bytes(int K) { return 64 * dec4_spl(K) + K / 2; }     // a packed row: the scale head, then the codes
+
+template <typename TO, bool GLU, bool SEP>
+static int launch_decode_gemv_w4(DecW4Args p, hipStream_t st) {
+  const int bpc = 4;                                   // workgroups per CU the row pairs are spread over, as vg_decode_gemv_w8
+  const int npair = GLU ? p.N : (p.N + 1) / 2;
+  const int maxw = 256 * bpc * 4;
+  int ppw = (npair + maxw - 1) / maxw;                 // row pairs per wave
+  for (int c = ppw; c <= 2 * ppw; ++c)                 // prefer whole rounds of 256 workgroups
+    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
+  if (ppw > DEC4_MAX_PPW) ppw = DEC4_MAX_PPW;
+  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
+  p.ppw = ppw;
+  const size_t lds = (size_t)p.K * 2;
+  switch (p.K) {
+    case 3072: decode_gemv_w4_kernel<TO, GLU, 96, SEP><<<blocks, 256, lds, st>>>(p); break;
+    case 4096: decode_gemv_w4_kernel<TO, GLU, 128, SEP><<<blocks, 256, lds, st>>>(p); break;
+    case 8192: decode_gemv_w4_kernel<TO, GLU, 256, SEP><<<blocks, 256, lds, st>>>(p); break;
+    default: decode_gemv_w4_kernel<TO, GLU, 448, SEP><<<blocks, 256, lds, st>>>(p); break;
+  }
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_decode_gemv_w4(const void* x, const uint8_t* W4, int64_t ldw_bytes, const uint8_t* scales, void* y, const float* norm_w, float eps,
+                                 const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream) {
+  VG_CHECK(x && W4 && y && N > 0 && K > 0, VG_ERR_ARG, "vg_decode_gemv_w4: bad args N=%d K=%d", N, K);
+  VG_CHECK(dec4_spl(K), VG_ERR_UNSUPPORTED, "vg_decode_gemv_w4: K=%d is not one of the supported row lengths (3072, 4096, 8192, 14336)", K);
+  const int64_t need = scales ? K / 2 : dec4_row_bytes(K);
+  VG_CHECK(ldw_bytes % 16 == 0 && ldw_bytes >= need, VG_ERR_ARG, "vg_decode_gemv_w4: ldw_bytes=%lld must be a multiple of 16 and at least %lld (K=%d, %s)",
+           (long long)ldw_bytes, (long long)need, K, scales ? "separate scales" : "packed rows");
+  VG_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)W4 & 15) == 0 && ((uintptr_t)norm_w & 15) == 0, VG_ERR_ARG,
+           "vg_decode_gemv_w4: x/W4/norm_w must be 16-byte aligned");
+  VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemv_w4: bad out_dtype %d", out_dtype);
+  DecW4Args p{x, W4, scales, y, norm_w, R, N, K, ldw_bytes, eps, 1};
+  hipStream_t st = (hipStream_t)stream;
+#define VG_DEC_W4(TOO, G) return scales ? launch_decode_gemv_w4<TOO, G, true>(p, st) : launch_decode_gemv_w4<TOO, G, false>(p, st)
+  if (out_dtype == VG_BF16) {
+    if (glu) VG_DEC_W4(bf16_t, true);
+    VG_DEC_W4(bf16_t, false);
+  }
+  if (glu) VG_DEC_W4(float, true);
+  VG_DEC_W4(float, false);
+#undef VG_DEC_W4
+}

@@ -123,7 +123,8 @@ class VideoGLaMMForCausalLM:
         for k in ("load_in_8bit", "load_in_4bit", "quantization_config"):
             if kwargs.get(k):
                 raise NotImplementedError(f"{k}: bitsandbytes quantisation (R/chat.py:247-272) is CUDA-only; the fp8 LLM path of this build is "
-                                          "cfg['llm']['decode_weights'] = cfg['llm']['prefill_gemm'] = 'fp8'")
+                                          "cfg['llm']['decode_weights'] = cfg['llm']['prefill_gemm'] = 'fp8', and the native 4-bit (MXFP4) decode "
+                                          "weights are cfg['llm']['decode_weights'] = 'mxfp4'")
         self.dtype = torch_dtype
         self.device = torch.device(device)
         if self.device.type == "cuda":
@@ -394,11 +395,14 @@ class VideoGLaMMForCausalLM:
         return feats, join
 
     def inference_framewise(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                            max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
-        """R/model/VideoGLaMM.py:598-768 -> (output_ids [1,L+G], [ {frame: {obj: mask}} ])."""
+                            max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None, empty_ok=False):
+        """R/model/VideoGLaMM.py:598-768 -> (output_ids [1,L+G], [ {frame: {obj: mask}} ]).  empty_ok: no [SEG] gives [{}] as the video branch
+        does, not the reference's exception (inference_prompts' meaning of such a prompt)."""
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens)
+        if emb.shape[0] == 0 and empty_ok:
+            return out_ids, [{}]
         if emb.shape[0] == 0:
             # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
             raise AttributeError("'tuple' object has no attribute 'shape'")
@@ -471,7 +475,9 @@ class VideoGLaMMForCausalLM:
         Entry b means what inference(..., input_ids=input_ids_list[b]) means; a prompt without a [SEG] gets {} (as the video branch does,
         R/model/VideoGLaMM.py:840-842).  The towers, Hiera and the prefill of the shared prefix (system text + visual block, identical ids in
         every prompt) run once; SAM2 runs once with every prompt's [SEG] embeddings as its objects.  Sampling draws one seed per prompt from
-        `generator`, in list order.  More than 16 prompts run in consecutive groups of 16."""
+        `generator`, in list order.  More than 16 prompts run in consecutive groups of 16.
+        A model with cfg["llm"]["decode_weights"] = "mxfp4" shares nothing yet: there is no B-row MXFP4 GEMV, and its entries are computed by the
+        very calls inference() makes, one prompt after another (ids and masks equal inference()'s bit for bit)."""
         from .prompts import GROUP, check_prompts
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_prompts() runs on one GPU: call inference() per prompt on a multi-GPU model")
@@ -489,6 +495,10 @@ class VideoGLaMMForCausalLM:
         check_prompts(ids_list)
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             torch.cuda.set_device(self.device)
+        if self._live_cfg()["llm"].get("decode_weights") == "mxfp4":
+            return self._prompts_alone(images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens,
+                                       use_sam2_video_branch, dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                                                   generator=generator))
         samplings = [resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator) for _ in ids_list]
         out_ids, segs = [], []
         for g in range(0, len(ids_list), GROUP):
@@ -496,6 +506,32 @@ class VideoGLaMMForCausalLM:
                                        use_sam2_video_branch, samplings[g:g + GROUP])
             out_ids += o
             segs += s
+        return out_ids, segs
+
+    def _prompts_alone(self, images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens, video, sampling):
+        """inference_prompts() as one inference() per prompt, in list order (each call draws its own sampling seed from the generator); the
+        captures of the calls are gathered per prompt as _prompts_group leaves them."""
+        out_ids, segs, caps = [], [], []
+        keep = self.capture
+        try:
+            for ids in ids_list:
+                if keep is not None:
+                    self.capture = {}
+                if video:
+                    o, s = self.inference_video_branch(images, context_images, images_for_sam, ids[None], resize_list, original_size_list,
+                                                       max_new_tokens, **sampling)
+                else:
+                    o, s = self.inference_framewise(images, context_images, images_for_sam, ids[None], resize_list, original_size_list,
+                                                    max_new_tokens, empty_ok=True, **sampling)
+                out_ids.append(o)
+                segs.append(s[0])
+                caps.append(self.capture)
+        finally:
+            self.capture = keep
+        if keep is not None:
+            for k in ("argmax", "emb", "logits"):
+                if any(k in c for c in caps):
+                    keep[k] = [c.get(k) for c in caps]
         return out_ids, segs
 
     def _prompts_group(self, images, context_images, images_for_sam, ids_list, original_size_list, max_new_tokens, video, samplings):

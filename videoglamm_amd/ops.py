@@ -641,6 +641,81 @@ def decode_gemv_w8(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=False
     return y
 
 
+MXFP4_K = {3072: 2, 4096: 2, 8192: 4, 14336: 8}      # row lengths of vg_decode_gemv_w4 -> SPL, scale bytes per lane in a packed row's head
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4_rows(w):
+    """[N,K] weight (K a multiple of 32) -> (uint8 [N,K/2] e2m1 codes, uint8 [N,K/32] e8m0 scales) by the OCP Microscaling v1.0 rule: per block
+    of 32 consecutive K elements the scale 2^e, e = floor(log2(amax)) - 2 (clamped to [-127, 127]; byte e + 127; an all-zero block: byte 0 and zero
+    codes), the elements w / 2^e rounded to nearest (ties to the even code) onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating at 6, sign in bit 3.
+    Logical layout: element 2j in the low nibble of byte j (torch.float4_e2m1fn_x2's).  One-time load work (torch, any device)."""
+    N, K = w.shape
+    assert K % 32 == 0, "MXFP4 blocks are 32 consecutive K elements"
+    b = w.float().reshape(N, K // 32, 32)
+    amax = b.abs().amax(dim=-1)
+    _, ex = torch.frexp(amax)                                # amax = m * 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = torch.where(amax > 0, (ex - 3).clamp(-127, 127), torch.full_like(ex, -127)).to(torch.int32)
+    h = -(e // 2)
+    a = torch.ldexp(torch.ldexp(b, h[..., None]), (-e - h)[..., None])     # w / 2^e, exact (two steps: 2^127 and 2^-127 stay normal factors)
+    m = a.abs()
+    # code = the number of midpoints passed; a tie stays below the midpoints whose lower neighbour is the even code (0 | .5, 1 | 1.5, 2 | 3, 4 | 6)
+    code = ((m > 0.25).to(torch.uint8) + (m >= 0.75) + (m > 1.25) + (m >= 1.75) + (m > 2.5) + (m >= 3.5) + (m > 5.0)).to(torch.uint8)
+    code = code | (torch.signbit(a).to(torch.uint8) << 3)
+    code = code.reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def mxfp4_pack(codes, scales):
+    """logical (codes [N,K/2], scales [N,K/32]) -> the packed rows vg_decode_gemv_w4 streams (uint8 [N, 64 * SPL + K/2], include/vg_kernels.h): a
+    head of 64 * SPL scale bytes — byte lane * SPL + u = the scale of block 64 u + lane, 0 where there is no such block — then the codes."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    assert K in MXFP4_K and scales.shape == (N, K // 32) and codes.dtype == torch.uint8 and scales.dtype == torch.uint8
+    spl = MXFP4_K[K]
+    head = torch.zeros(N, spl * 64, dtype=torch.uint8, device=codes.device)
+    head[:, : K // 32] = scales                              # [u][lane] order, zero-padded to spl * 64 blocks
+    head = head.view(N, spl, 64).transpose(1, 2).reshape(N, 64 * spl)
+    return torch.cat([head, codes], dim=1).contiguous()
+
+
+def mxfp4_dequant(codes, scales=None, K=None):
+    """the float32 [N,K] tensor an MXFP4 weight means: logical (codes, scales), or packed rows (scales None; K from the row length).  torch, any device."""
+    if scales is None:
+        K = K or next(k for k, s in MXFP4_K.items() if 64 * s + k // 2 == codes.shape[1])
+        spl = MXFP4_K[K]
+        head = codes[:, : 64 * spl].reshape(-1, 64, spl).transpose(1, 2).reshape(-1, 64 * spl)
+        scales, codes = head[:, : K // 32], codes[:, 64 * spl:]
+    N, K = codes.shape[0], codes.shape[1] * 2
+    nib = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(N, K).long()
+    grid = torch.tensor(_E2M1, dtype=torch.float32, device=codes.device)
+    val = torch.where((nib & 8) != 0, -grid[nib & 7], grid[nib & 7]).reshape(N, K // 32, 32)
+    e = scales.to(torch.int32) - 127
+    h = e // 2
+    return torch.ldexp(torch.ldexp(val, h[..., None]), (e - h)[..., None]).reshape(N, K)
+
+
+def decode_gemv_w4(x, w4, scales=None, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """decode_gemv with MXFP4 weights (vg_decode_gemv_w4): x bf16 [1,K]; w4 uint8, N or 2N rows: packed rows (mxfp4_pack; scales None) or the
+    logical codes [rows, K/2] with scales uint8 [rows, K/32]."""
+    lib = _lib.load()
+    K = x.shape[-1]
+    assert x.dtype == torch.bfloat16 and x.numel() == K and x.is_contiguous() and w4.dtype == torch.uint8 and w4.stride(1) == 1
+    if scales is not None:
+        assert scales.dtype == torch.uint8 and scales.shape == (w4.shape[0], K // 32) and scales.is_contiguous() and w4.shape[1] == K // 2
+    else:
+        assert K not in MXFP4_K or w4.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
+    N = w4.shape[0] // 2 if glu else w4.shape[0]
+    odt = out_dtype or x.dtype
+    y = out if out is not None else torch.empty(1, N, dtype=odt, device=x.device)
+    assert y.is_contiguous() and y.numel() == N
+    if residual is not None:
+        assert residual.is_contiguous() and residual.numel() == N and residual.dtype == y.dtype
+    rc = lib.vg_decode_gemv_w4(_p(x), _p(w4), w4.stride(0), _p(scales), _p(y), _p(None if norm_w is None else _f32(norm_w)), float(eps),
+                               _p(residual), N, K, int(bool(glu)), _dt(y), _stream())
+    _lib.check(rc, "vg_decode_gemv_w4")
+    return y
+
+
 def decode_attention_workspace(H, Hkv, D, max_len, device):
     """zero-filled once: the workspace ends with per-KV-head arrival counters that the kernel resets itself."""
     n = _lib.load().vg_decode_attention_ws_floats(H, Hkv, D, max_len)

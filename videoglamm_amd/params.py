@@ -83,6 +83,19 @@ class Params:
             return ops.quantize_fp8_rows(w)
         return self._get(("fp8",) + tuple(names), make)
 
+    def fp4(self, names, stored=None):
+        """fused()/w() of the named weights as MXFP4 for the decode GEMVs (cfg decode_weights = "mxfp4"): the packed rows of ops.mxfp4_pack
+        (uint8 [N, scale head + K/2]: e2m1 codes, one e8m0 scale per 32 K elements).  Made once from the packed model-dtype weight and kept beside
+        it, as fp8(); the prefill GEMMs stay in the model dtype."""
+        from . import ops
+
+        names = [names] if isinstance(names, str) else list(names)
+
+        def make():
+            w = self.w(names[0]) if len(names) == 1 and stored is None else self.fused(names, stored=stored)[0]
+            return ops.mxfp4_pack(*ops.quantize_mxfp4_rows(w))
+        return self._get(("fp4",) + tuple(names), make)
+
     # ---- convolutions as GEMMs
     def conv_w(self, name):
         """Conv2d [Cout,Cin,kh,kw] (or Conv3d with kt=1) -> [Cout, (ky*kw+kx)*Cin + c] padded (vg_im2col column order)."""

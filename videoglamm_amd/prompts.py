@@ -33,13 +33,15 @@ def sampling_route(sampling, vocab):
     return "sample_fast" if ops.sample_fast_route(int(sampling["k"]), vocab) else "sample"
 
 
-def batched_route(B, rope_path, decode_weights, chain, routes, env, attn_rows=False, w8_rows=False):
+def batched_route(B, rope_path, decode_weights, chain, routes, env, attn_rows=False, w8_rows=False, w4_rows=False):
     """True when a group of B prompts decodes in one batched step (RowsDecode) instead of one after another.  rope_path: the decoder runs the
     bf16 head_dim-128 rope step (LlamaDecoder.rope_path; B-row kernels cover the shape); attn_rows: the decoder runs the decode_attention step
     (Phi-3-mini width) and the B-row kernels cover its shape (ops.decode_step_rows_supported); decode_weights: cfg["decode_weights"] ("fp8" takes
-    the batched step only with w8_rows: the B-row fp8 GEMV covers this decoder's MLP and lm_head row lengths); chain: VG_DECODE_CHAIN roles; routes: the set of the prompts' sampling routes; env: the environment (VG_PROMPTS_BATCHED=0 forces the sequential loop;
+    the batched step only with w8_rows: the B-row fp8 GEMV covers this decoder's MLP and lm_head row lengths; "mxfp4" only with w4_rows: a B-row MXFP4 GEMV — there is none yet, so
+    generate_prompts keeps the sequential loop for such a model, and model.inference_prompts() runs its prompts as inference() does); chain: VG_DECODE_CHAIN roles; routes: the set of the prompts' sampling routes; env: the environment (VG_PROMPTS_BATCHED=0 forces the sequential loop;
     VG_DECODE_AHEAD=1 keeps it too).  Pure: no device work."""
-    return (B >= 2 and B <= BUCKETS[-1] and (bool(rope_path) or bool(attn_rows)) and (decode_weights != "fp8" or bool(w8_rows)) and not chain and len(set(routes)) == 1
+    return (B >= 2 and B <= BUCKETS[-1] and (bool(rope_path) or bool(attn_rows)) and (decode_weights != "fp8" or bool(w8_rows)) and (decode_weights != "mxfp4" or bool(w4_rows))
+            and not chain and len(set(routes)) == 1
             and env.get("VG_PROMPTS_BATCHED", "1") != "0" and env.get("VG_DECODE_AHEAD", "0") != "1")
 
 
@@ -109,7 +111,7 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
     # fp8 decode weights: gate|up and the lm_head run at K = hidden, down at K = ffn
     w8_rows = dec.w8 and ops.decode_gemv_w8_rows_supported(dec.D) and ops.decode_gemv_w8_rows_supported(_ffn(params))
     batched = max_new_tokens > 1 and batched_route(B, rope_rows, cfg["llm"].get("decode_weights"), dec.chain_roles, routes, os.environ,
-                                                   attn_rows=attn_rows, w8_rows=w8_rows)
+                                                   attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=False)     # no B-row MXFP4 GEMV: "mxfp4" takes the sequential loop
     rows = None
     if batched:
         row0, n_bound = slot_layout(P, dec.kpw2 if dec.rope_path else RowsDecode.ATTN_KW, need)

@@ -213,6 +213,9 @@ class LlamaDecoder:
         # fp8 (e4m3) weights with per-row scales in the decode step's MLP GEMVs and the lm_head (cfg["decode_weights"] == "fp8": the decode
         # side of BASELINE config C4's "fp8 LLM path"; bf16 activations, fp32 accumulation; the prefill GEMMs stay bf16)
         self.w8 = c.get("decode_weights") == "fp8"
+        # MXFP4 weights (e2m1 codes, one e8m0 scale per 32 K elements) in the decode step's MLP GEMVs (cfg["decode_weights"] == "mxfp4"); the lm_head
+        # takes the fp8 GEMV (it decides the token ids and is 4 % of the remaining bytes), the attention projections stay bf16 as under "fp8"
+        self.w4 = c.get("decode_weights") == "mxfp4"
         # fp8 MFMA prefill GEMMs (cfg["prefill_gemm"] == "fp8"): vg_quantize_fp8_rows + vg_gemm_f8; the attention itself stays bf16
         self.f8_prefill = c.get("prefill_gemm") == "fp8"
         assert not self.f8_prefill or dt == torch.bfloat16, "the fp8 prefill pairs with a bf16 model"
@@ -221,7 +224,9 @@ class LlamaDecoder:
         self.fused_decode = (os.environ.get("VG_DECODE_FUSED", "1") != "0" and (self.H // self.Hkv) in (1, 2, 4, 8)
                              and self.hd % (16 // es) == 0 and self.hd * es <= 512 and max_len <= 8192
                              and max(self.D, ffn) * es <= 65536 and self.D % (16 // es) == 0 and ffn % (16 // es) == 0)
-        assert self.fused_decode or not self.w8, "fp8 decode weights need the fused decode kernels"
+        if self.w4:
+            assert dt == torch.bfloat16 and self.D in (3072, 4096, 8192) and ffn in (8192, 14336), "mxfp4 decode weights: bf16 model, supported row lengths"
+        assert self.fused_decode or not (self.w8 or self.w4), "fp8 / mxfp4 decode weights need the fused decode kernels"
         # vg_decode_layer: which roles of a layer run as one chained launch.  VG_DECODE_CHAIN=1 (attention + o_proj) / 3 (+ the MLP); default 0 =
         # separate launches: measured on C2 the chained launch only ties (27.4 us vs 20.1 + 8.0; 85.4 vs 84.7 for the whole layer — every
         # device-side hand-off is a fabric round trip, as the launch boundary it replaces is)
@@ -335,7 +340,7 @@ class LlamaDecoder:
                 # r03: attention, o_proj and (bf16 Llama widths) the MLP as roles of ONE launch whose GEMV workgroups fetch their weight
                 # rows while the producer role still runs (vg_decode_layer) — bit-identical to the separate launches below
                 w_o = P.w(l + "self_attn.o_proj")
-                if self.chain_roles == 3 and not self.w8:
+                if self.chain_roles == 3 and not (self.w8 or self.w4):     # the chained MLP role streams bf16 weights only
                     wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
                     x = ops.decode_layer(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5,
                                          self.attn_ws, self.chain_flags[i], w_o, x, window=self.window,
@@ -353,6 +358,10 @@ class LlamaDecoder:
                 a = ops.decode_gemv_w8(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
                                        eps=c["rms_eps"], glu=True)
                 x = ops.decode_gemv_w8(a, *P.fp8(l + "mlp.down_proj"), residual=x)
+            elif self.w4:
+                a = ops.decode_gemv_w4(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                                       eps=c["rms_eps"], glu=True)
+                x = ops.decode_gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
             else:
                 wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
                 a = ops.decode_gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
@@ -411,7 +420,7 @@ class LlamaDecoder:
 
     def next_token(self, hidden_row):
         """lm_head + argmax (or, sampling, the warpers + the draw of step *step_dev) of one final-norm row -> tok_dev (device int64[1])."""
-        if self.w8 and hidden_row.shape[0] == 1:
+        if (self.w8 or self.w4) and hidden_row.shape[0] == 1:
             logits = ops.decode_gemv_w8(hidden_row.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(hidden_row, self.P.w("lm_head"), out_dtype=torch.float32)
@@ -433,7 +442,7 @@ class LlamaDecoder:
         x = ops.decode_step_begin(self.tok_dev, self.P.t("model.embed_tokens.weight"), self.pos_dev,
                                   rope=(self.cos, self.sin, self.rope_cs) if self.rope_path else None)
         h = self._layers_decode(x, rope_row=False)
-        if self.w8:
+        if self.w8 or self.w4:
             logits = ops.decode_gemv_w8(h.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(h, self.P.w("lm_head"), out_dtype=torch.float32)
@@ -508,6 +517,7 @@ class RowsDecode:
         d, dev, dt = dec, dec.P.device, dec.P.dtype
         B = bucket
         self.attn_rows = not d.rope_path
+        assert not d.w4, "no B-row MXFP4 GEMV: an mxfp4 decoder decodes its prompts one after another (prompts.batched_route)"
         assert row0 % (self.ATTN_KW if self.attn_rows else d.kpw2) == 0
         rows = n_bound - row0
         self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]

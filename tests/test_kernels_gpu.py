@@ -113,7 +113,9 @@ def test_decode_gemv(cuda, dtype, N, K):
     nw = (1.0 + 0.1 * rnd(K, seed=3)).to(dtype).float()
     res = rnd(1, N, dtype=dtype, seed=4)
     gx, gw, gnw, gres = x.to(cuda), w.to(cuda), nw.to(cuda), res.to(cuda)
-    t = tol(dtype, K)
+    # bf16: the outputs are ~N(0, 1) whatever K is (w carries K^-0.5), so the tolerance does not grow with K — tol(bf16, 14336) would let a result
+    # through that lost a whole 64-element K step in every output (tests/test_contraction_exact_selfcheck.py records it)
+    t = tol(dtype, K) if dtype == torch.float32 else dict(rtol=2e-2, atol=2e-2)
     close(ops.decode_gemv(gx, gw[:N]), ref.linear(x, w[:N]), **t)
     close(ops.decode_gemv(gx, gw[:N], residual=gres), ref.linear(x, w[:N], residual=res), **t)
     close(ops.decode_gemv(gx, gw[:N], norm_w=gnw, eps=1e-5), ref.linear(ref.rmsnorm(x, nw, 1e-5), w[:N]), **t)
@@ -893,9 +895,10 @@ def test_gemm_splitk(cuda, dtype, M, N, K, monkeypatch):
     assert ops._splitk(M, N, K, 2 if dtype == torch.bfloat16 else 4) >= 2      # every case here is routed to split-K
     x, w = rnd(M, K, dtype=dtype, seed=1), rnd(N, K, dtype=dtype, seed=2, scale=K ** -0.5)
     bias, gamma, res = rnd(N, seed=3), 1.0 + 0.1 * rnd(N, seed=4), rnd(M, N, dtype=dtype, seed=5)
+    t = tol(dtype, K) if dtype == torch.float32 else dict(rtol=2e-2, atol=2e-2)      # bf16: unit-scale outputs, the tolerance of test_gemm_p8 / test_gemm_p8n
     y = ops.linear(x.to(cuda), w.to(cuda), bias.to(cuda), act=ops.ACT_GELU, gamma=gamma.to(cuda), residual=res.to(cuda))
-    close(y, ref.linear(x, w, bias, act=ref.ACT_GELU, gamma=gamma, residual=res), **tol(dtype, K))
-    close(ops.linear(x.to(cuda), w.to(cuda)), ref.linear(x, w), **tol(dtype, K))
+    close(y, ref.linear(x, w, bias, act=ref.ACT_GELU, gamma=gamma, residual=res), **t)
+    close(ops.linear(x.to(cuda), w.to(cuda)), ref.linear(x, w), **t)
 
 
 BIG = [  # (M, N, K, glu): bf16 shapes the launcher routes to the 256x256-tile kernels (vg_gemm_route == 3) — the LLM prefill GEMMs of C1 / C2

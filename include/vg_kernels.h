@@ -465,6 +465,18 @@ int vg_decode_gemv_w8(const void* x, const uint8_t* W8, int64_t ldw, const float
  * ldw_bytes a multiple of 16 that covers the row; x, W4, norm_w 16-byte aligned. */
 int vg_decode_gemv_w4(const void* x, const uint8_t* W4, int64_t ldw_bytes, const uint8_t* scales, void* y, const float* norm_w, float eps,
                       const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream);
+/* vg_decode_gemv_w4 for B rows (the MLP of the batched step with MXFP4 decode weights): x[b] = x + b * ldx (bf16, K elements), W4 PACKED rows only
+ * (the decoder's form: row n at W4 + n * ldw_bytes = the head of 64 * SPL scale bytes, then the K / 2 code bytes; the separate-scales layout of the
+ * single-row entry point is not needed here and has no B-row form), y[b] = y + b * ldy (out_dtype VG_BF16 | VG_F32), residual R + b * ldr of the
+ * output dtype, norm_w / eps and glu as vg_decode_gemv_w4.  Row b is bit-identical to vg_decode_gemv_w4 on row b alone; every weight byte is read
+ * once per launch and converted once for the B rows.  B in [1, 16], staged in buckets of 1, 2, 4, 8, 16 rows (a bucket row beyond B re-reads row
+ * B - 1 and is not written); K must be one of 3072, 4096, 8192, 14336 (vg_decode_gemv_w4_rows_supported(K) != 0), VG_ERR_UNSUPPORTED otherwise;
+ * ldw_bytes a multiple of 16 that covers a packed row, ldx a multiple of 8, x, W4 and norm_w 16-byte aligned.  LDS: without a norm the rows are
+ * staged in phases of at most 64 KiB; with a norm the whole rows of the bucket are staged, so bucket x K x 2 bytes must fit 152 KiB (K <= 4096 at
+ * 16 rows), VG_ERR_UNSUPPORTED otherwise. */
+int vg_decode_gemv_w4_rows_supported(int K);
+int vg_decode_gemv_w4_rows(const void* x, int64_t ldx, const uint8_t* W4, int64_t ldw_bytes, void* y, int64_t ldy, const float* norm_w, float eps,
+                           const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream);
 /* vg_gemm for grids that leave most of the chip idle (few 128x128 tiles, long K): K is cut into ksplit slices that run as
  * separate workgroups, the fp32 partial tiles go to `workspace` (>= ksplit*M*N floats) and one pass sums them and applies
  * bias / act / gamma / residual.  Same result up to fp32 summation order.  M > 16, N % 8 == 0, no batch / GLU / window. */

@@ -10,10 +10,12 @@ differ in their 30 question ids.  One JSON line per LLM:
   "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode: Llama-3 and Phi-3-mini widths), ms per step
 --decode-weights fp8 / --prefill fp8: the fp8 LLM path (bench.py's switches of the same names), written into each line.
 --ab also times inference_prompts() with VG_PROMPTS_BATCHED=0 ("prompts_seq_ms"[B]: the prompts decoded one after another).
+--shared passes shared=True: the shared route for every model.  An mxfp4 model takes it only then (its default is one inference() per prompt, which
+is what "sequential_ms" times), so --decode-weights mxfp4 --shared --ab compares the batched MXFP4 step with the sequential loop on that route.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 
     python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise]
-                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--ab] [--out FILE]
+                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--shared] [--ab] [--out FILE]
 """
 import argparse
 import json
@@ -97,21 +99,22 @@ def run(llm, args, device):
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
     rec = dict(llm=llm, decode_weights=args.decode_weights, prefill=args.prefill, branch=args.branch, frames=args.frames,
-               max_new_tokens=args.max_new_tokens, prompts_ms={}, sequential_ms={}, ratio={},
+               max_new_tokens=args.max_new_tokens, shared=args.shared, prompts_ms={}, sequential_ms={}, ratio={},
                rows_step_ms={})
+    kw = dict(shared=True) if args.shared else {}
     if args.ab:
         rec["prompts_seq_ms"] = {}
     for B in args.batches:
         P = prompts[:B]
         seq = timed(lambda: [model.inference(images, context, sam, x[None], *rest, args.max_new_tokens, video) for x in P], args.steps, args.warmup)
-        bat = timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video), args.steps, args.warmup)
+        bat = timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video, **kw), args.steps, args.warmup)
         rec["prompts_ms"][B], rec["sequential_ms"][B], rec["ratio"][B] = round(bat, 2), round(seq, 2), round(bat / seq, 3)
         rec["rows_step_ms"][B] = rows_step_ms(model) if B > 1 else None
         if args.ab:
             os.environ["VG_PROMPTS_BATCHED"] = "0"
             try:
-                rec["prompts_seq_ms"][B] = round(timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video),
-                                                       args.steps, args.warmup), 2)
+                rec["prompts_seq_ms"][B] = round(timed(lambda: model.inference_prompts(images, context, sam, P, *rest, args.max_new_tokens, video,
+                                                                                       **kw), args.steps, args.warmup), 2)
             finally:
                 os.environ.pop("VG_PROMPTS_BATCHED")
     rec["decode_step_ms"] = decode_step_ms(model)
@@ -132,8 +135,10 @@ def main():
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
     ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="fp8: the decode step's MLP and lm_head weights in fp8 (e4m3, row scales), as bench.py --decode-weights; mxfp4: the MLP in MXFP4, "
-                         "the lm_head in fp8 (inference_prompts() runs such a model's prompts as one inference() each: there is no B-row MXFP4 GEMV)")
+                         "the lm_head in fp8 (by default inference_prompts() runs such a model's prompts as one inference() each; --shared sends it down "
+                         "the shared route, where the prompts decode on the B-row MXFP4 GEMV)")
     ap.add_argument("--prefill", default="bf16", choices=["bf16", "fp8"], help="fp8: the LLM prefill GEMMs on the fp8 MFMA path, as bench.py --prefill")
+    ap.add_argument("--shared", action="store_true", help="call inference_prompts(..., shared=True): the shared route for every model, mxfp4 included")
     ap.add_argument("--ab", action="store_true", help="also time inference_prompts() on the sequential loop (VG_PROMPTS_BATCHED=0)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()

@@ -58,6 +58,8 @@ def _sig(lib):
         "vg_decode_gemv_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_gemv_w8_rows_supported": ([I], c_int),
         "vg_decode_gemv_w8_rows": ([P, L, P, L, P, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
+        "vg_decode_gemv_w4_rows_supported": ([I], c_int),
+        "vg_decode_gemv_w4_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_qkv_rope_rows": ([P, L, P, L, P, F, P, L, P, P, L, I, I, P, P, I, I, I, I, I, I, P], c_int),
         "vg_decode_attention2_rows_ws_floats": ([I, I, I, I, I, I], c_int64),
         "vg_decode_attention2_rows": ([P, P, P, I, P, P, L, I, I, P, I, I, I, I, I, F, P, P, L, I, I, I, P], c_int),

@@ -470,14 +470,16 @@ class VideoGLaMMForCausalLM:
     # ------------------------------------------------------------------ several prompts about one clip
     def inference_prompts(self, images, context_images, images_for_sam, input_ids_list, resize_list, original_size_list,
                           max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                          generator=None):
+                          generator=None, shared=None):
         """B prompts ([1, L_b] or [L_b] each) about ONE clip -> (output ids [1, L_b + G_b] per prompt, {frame: {obj: mask}} per prompt).
         Entry b means what inference(..., input_ids=input_ids_list[b]) means; a prompt without a [SEG] gets {} (as the video branch does,
         R/model/VideoGLaMM.py:840-842).  The towers, Hiera and the prefill of the shared prefix (system text + visual block, identical ids in
         every prompt) run once; SAM2 runs once with every prompt's [SEG] embeddings as its objects.  Sampling draws one seed per prompt from
         `generator`, in list order.  More than 16 prompts run in consecutive groups of 16.
-        A model with cfg["llm"]["decode_weights"] = "mxfp4" shares nothing yet: there is no B-row MXFP4 GEMV, and its entries are computed by the
-        very calls inference() makes, one prompt after another (ids and masks equal inference()'s bit for bit)."""
+        shared picks the route.  True: the shared route just described, for any model (the decode is one batched step per token wherever
+        prompts.batched_route allows it — bf16, fp8 and mxfp4 decode weights).  False: one inference() call per prompt, in list order, for any model:
+        nothing is shared, and ids and masks equal inference()'s bit for bit (the shared route's masks need not).  None (the default):
+        the shared route, except for a model with cfg["llm"]["decode_weights"] = "mxfp4", which keeps the per-prompt calls it has always had."""
         from .prompts import GROUP, check_prompts
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_prompts() runs on one GPU: call inference() per prompt on a multi-GPU model")
@@ -495,7 +497,9 @@ class VideoGLaMMForCausalLM:
         check_prompts(ids_list)
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             torch.cuda.set_device(self.device)
-        if self._live_cfg()["llm"].get("decode_weights") == "mxfp4":
+        if shared is None:
+            shared = self._live_cfg()["llm"].get("decode_weights") != "mxfp4"
+        if not shared:
             return self._prompts_alone(images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens,
                                        use_sam2_video_branch, dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                                                    generator=generator))

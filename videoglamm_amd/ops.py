@@ -927,6 +927,31 @@ def decode_gemv_w8_rows(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=
     return y
 
 
+def decode_gemv_w4_rows_supported(K):
+    """True when the B-row MXFP4 GEMV has the row length K (vg_decode_gemv_w4_rows_supported: 3072, 4096, 8192, 14336)."""
+    return bool(_lib.load().vg_decode_gemv_w4_rows_supported(int(K)))
+
+
+def decode_gemv_w4_rows(x, w4, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """decode_gemv_w4 on each of the B rows of x [B,K] (vg_decode_gemv_w4_rows): one pass over the packed MXFP4 rows (mxfp4_pack) for all rows
+    -> [B,N]."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w4.dtype == torch.uint8 and w4.stride(1) == 1
+    assert K not in MXFP4_K or w4.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
+    N = w4.shape[0] // 2 if glu else w4.shape[0]
+    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
+    assert y.shape == (B, N) and y.stride(1) == 1
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
+        ldr = residual.stride(0)
+    rc = lib.vg_decode_gemv_w4_rows(_p(x), x.stride(0), _p(w4), w4.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)),
+                                    float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y), _stream())
+    _lib.check(rc, "vg_decode_gemv_w4_rows")
+    return y
+
+
 def decode_qkv_rope_rows(x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out=None):
     """decode_qkv_rope on each row of x [B,K]: row b at position pos_dev[b] with rope_cs[b], its K / V rows into slot b of k_slots / v_slots
     ([B, rows, Hkv, D], row j of the sequence at j - row0) -> rotated q [B, H*D]."""

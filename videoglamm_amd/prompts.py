@@ -37,8 +37,8 @@ def batched_route(B, rope_path, decode_weights, chain, routes, env, attn_rows=Fa
     """True when a group of B prompts decodes in one batched step (RowsDecode) instead of one after another.  rope_path: the decoder runs the
     bf16 head_dim-128 rope step (LlamaDecoder.rope_path; B-row kernels cover the shape); attn_rows: the decoder runs the decode_attention step
     (Phi-3-mini width) and the B-row kernels cover its shape (ops.decode_step_rows_supported); decode_weights: cfg["decode_weights"] ("fp8" takes
-    the batched step only with w8_rows: the B-row fp8 GEMV covers this decoder's MLP and lm_head row lengths; "mxfp4" only with w4_rows: a B-row MXFP4 GEMV — there is none yet, so
-    generate_prompts keeps the sequential loop for such a model, and model.inference_prompts() runs its prompts as inference() does); chain: VG_DECODE_CHAIN roles; routes: the set of the prompts' sampling routes; env: the environment (VG_PROMPTS_BATCHED=0 forces the sequential loop;
+    the batched step only with w8_rows: the B-row fp8 GEMV covers this decoder's MLP and lm_head row lengths; "mxfp4" only with w4_rows: the B-row MXFP4 GEMV covers the MLP's row lengths and the B-row fp8 GEMV the lm_head's;
+    model.inference_prompts() reaches this route for an mxfp4 model with shared=True only); chain: VG_DECODE_CHAIN roles; routes: the set of the prompts' sampling routes; env: the environment (VG_PROMPTS_BATCHED=0 forces the sequential loop;
     VG_DECODE_AHEAD=1 keeps it too).  Pure: no device work."""
     return (B >= 2 and B <= BUCKETS[-1] and (bool(rope_path) or bool(attn_rows)) and (decode_weights != "fp8" or bool(w8_rows)) and (decode_weights != "mxfp4" or bool(w4_rows))
             and not chain and len(set(routes)) == 1
@@ -110,8 +110,11 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
                  and ops.decode_step_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype))
     # fp8 decode weights: gate|up and the lm_head run at K = hidden, down at K = ffn
     w8_rows = dec.w8 and ops.decode_gemv_w8_rows_supported(dec.D) and ops.decode_gemv_w8_rows_supported(_ffn(params))
+    # mxfp4 decode weights: gate|up at K = hidden and down at K = ffn on the B-row MXFP4 GEMV, the lm_head (fp8) at K = hidden
+    w4_rows = (dec.w4 and ops.decode_gemv_w4_rows_supported(dec.D) and ops.decode_gemv_w4_rows_supported(_ffn(params))
+               and ops.decode_gemv_w8_rows_supported(dec.D))
     batched = max_new_tokens > 1 and batched_route(B, rope_rows, cfg["llm"].get("decode_weights"), dec.chain_roles, routes, os.environ,
-                                                   attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=False)     # no B-row MXFP4 GEMV: "mxfp4" takes the sequential loop
+                                                   attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=w4_rows)
     rows = None
     if batched:
         row0, n_bound = slot_layout(P, dec.kpw2 if dec.rope_path else RowsDecode.ATTN_KW, need)

@@ -507,6 +507,8 @@ class RowsDecode:
     Two forms of the step, as the decoder's single-row step: the rope path (bf16 head_dim 128: q|k|v + RoPE + append, then vg_decode_attention2_rows;
     kw = dec.kpw2) and the decode_attention path (Phi-3-mini width: q|k|v GEMV, then RoPE + append + attention in vg_decode_attention_rows, whose
     rows pick 64 or 128 keys per workgroup on the device from their own position and dec.kpw_min; kw = ATTN_KW).
+    The projections follow the decoder's decode weights: bf16 (vg_decode_gemv_rows), fp8 (the MLP and the lm_head on vg_decode_gemv_w8_rows) or
+    mxfp4 (the MLP on vg_decode_gemv_w4_rows, the lm_head on vg_decode_gemv_w8_rows); the attention projections are bf16 in all three.
     The step is captured once per sampling route ("greedy" / "sample_fast" / "sample") into a HIP graph; a new seed or temperature is a copy into
     samp_params.  Rows past the live prompts (bucket padding) and retired rows keep computing into their own slots; their tokens are ignored."""
 
@@ -517,7 +519,6 @@ class RowsDecode:
         d, dev, dt = dec, dec.P.device, dec.P.dtype
         B = bucket
         self.attn_rows = not d.rope_path
-        assert not d.w4, "no B-row MXFP4 GEMV: an mxfp4 decoder decodes its prompts one after another (prompts.batched_route)"
         assert row0 % (self.ATTN_KW if self.attn_rows else d.kpw2) == 0
         rows = n_bound - row0
         self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
@@ -593,12 +594,18 @@ class RowsDecode:
                 a = ops.decode_gemv_w8_rows(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
                                             eps=c["rms_eps"], glu=True)
                 x = ops.decode_gemv_w8_rows(a, *P.fp8(l + "mlp.down_proj"), residual=x)
+            elif d.w4:
+                # MXFP4 decode weights: the MLP on the B-row MXFP4 GEMV (packed rows, Params.fp4), the lm_head (below) on the fp8 one — the
+                # operands of the single-row step
+                a = ops.decode_gemv_w4_rows(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                                            eps=c["rms_eps"], glu=True)
+                x = ops.decode_gemv_w4_rows(a, P.fp4(l + "mlp.down_proj"), residual=x)
             else:
                 wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
                 a = ops.decode_gemv_rows(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
                 x = ops.decode_gemv_rows(a, P.w(l + "mlp.down_proj"), residual=x)
         h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
-        if d.w8:
+        if d.w8 or d.w4:
             logits = ops.decode_gemv_w8_rows(h, *P.fp8("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(h, P.w("lm_head"), out_dtype=torch.float32)

@@ -287,12 +287,19 @@ int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const void* k_cache
  *   vg_decode_step_end consumes it.  fast_ws == NULL: the general route (one 1024-thread workgroup, any k).  fast_ws != NULL: the fast route
  *   for 1 <= k <= 64 and n <= 131072 (up to 64 workgroups + a last-arriver merge; tie overflow or another k falls back to the general route
  *   inside the launch); fast_ws = vg_sample_workspace_ints() int32, zero-filled once, one per stream (its ticket resets itself).  tok != NULL: *tok = the drawn index as well (either may be NULL, not both).  u = (philox4x32_10(key = seed, counter = (*step, 0, 0, 0))[0] >> 8) * 2^-24, or *u_override when not NULL (tests).
+ * vg_sample_partial_rows — vg_sample_partial on the B rows x[b * ldx .. b * ldx + n) of a batched decode step in ONE launch (ldx in elements, >= n).
+ *   Row b reads params + 24 b bytes, step[b] and (when not NULL) u_override[b], and writes acc[b] and / or tok[b]; each is bit-identical to
+ *   vg_sample_partial on row b alone.  fast_ws == NULL: one 1024-thread workgroup per row.  fast_ws != NULL: up to 64 workgroups per row;
+ *   fast_ws = B * vg_sample_workspace_ints() int32, zero-filled once — row b's candidates and self-resetting ticket live in its own slice, and a
+ *   tie overflow or a k outside 1..64 sends that row alone to the general route inside the launch.  1 <= B <= 65535.
  * vg_sample_survivors — the entries the warpers keep: idx[j] / prob[j] for j < min(*count, cap), in no particular order; *count (zero on entry)
  *   receives their number.  prob = softmax over the kept entries.
  * vg_sample_philox — out[i] = philox4x32_10(key = seeds[i], counter = (steps[i], 0, 0, 0))[0]. */
 int vg_sample_workspace_ints(void);
 int vg_sample_partial(const float* x, int n, const void* params, const int* step, const float* u_override, uint64_t* acc, int64_t* tok,
                       int* fast_ws, vg_stream_t stream);
+int vg_sample_partial_rows(const float* x, int64_t ldx, int n, int B, const void* params, const int* step, const float* u_override, uint64_t* acc,
+                           int64_t* tok, int* fast_ws, vg_stream_t stream);
 int vg_sample_survivors(const float* x, int n, const void* params, int64_t* idx, float* prob, int cap, int* count, vg_stream_t stream);
 int vg_sample_philox(const uint64_t* seeds, const int* steps, int n, uint32_t* out, vg_stream_t stream);
 

@@ -1,0 +1,113 @@
+"""Several clips, one prompt each: model.inference_clips() against the same clips as a loop of inference() calls.
+
+Workload: BASELINE config C2 (synthetic Llama-3-8B, 16 encoder frames, 32 x 1024^2 SAM frames, 32 new tokens, [SEG] forced at step 8 as
+bench.py does) x B, and the same with the Phi-3-mini LLM (--llm); the B entries are the same clip with B different questions (30 ids).
+The two forms alternate inside each repetition; one JSON line per (LLM, mode):
+  "clips_ms"[B] / "loop_ms"[B]:  median ms of one inference_clips() call with B clips / of the B inference() calls, over --reps repetitions
+  "clips_spread"[B] / "loop_spread"[B]: [min, max] of the repetitions
+  "clips_ms_per_clip"[B] / "loop_ms_per_clip"[B]: the medians / B
+  "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode with row0 = 0), rows at the clips' positions
+  "decode_step_ms":   one replayed single-row decode step (LlamaDecoder.decode_step), ms per token
+--sample k50 / k0: sampled decoding (k 50, p 0.9, T 0.6: the fast route; k 0, p 0.9: the general route), seeded per repetition.
+--out FILE also appends the lines to FILE (the raw record behind DESIGN 12's table lives in profiles/).
+
+    python tools/bench_clips.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8 16] [--reps 3] [--warmup 1] [--branch framewise]
+                                 [--sample k50 k0] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from videoglamm_amd import synth  # noqa: E402
+from videoglamm_amd.model import VideoGLaMMForCausalLM  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_prompts import decode_step_ms, rows_step_ms  # noqa: E402
+
+SAMPLING = {"greedy": {}, "k50": dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.6), "k0": dict(do_sample=True, top_k=0, top_p=0.9, temperature=1.0)}
+
+
+def once(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1000.0
+
+
+def run(llm, mode, args, device):
+    cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
+    cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
+    sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
+    model = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, cfg, torch_dtype=torch.bfloat16, device=device))
+    g = torch.Generator().manual_seed(1234)
+    te, S = 16, cfg["sam2"]["image_size"]
+    iv, cl = cfg["iv2"]["img_size"], cfg["clip"]["img_size"]
+    images = [torch.randn(te, 3, iv, iv, generator=g).to(device)]
+    context = [torch.randn(te, 3, cl, cl, generator=g).to(device)]
+    sam = [torch.randn(args.frames, 3, S, S, generator=g).to(device)]
+    head = torch.cat([torch.tensor([1, 5, 6]), torch.full((te,), -200)])
+    prompts = [torch.cat([head, torch.randint(3, cfg["llm"]["vocab"] - 2, (30,), generator=g)]) for _ in range(max(args.batches))]
+    rest = ([(1024, 1024)], [(args.src, args.src)])
+    video = args.branch == "video"
+    kw = dict(max_new_tokens=args.max_new_tokens, use_sam2_video_branch=video, **SAMPLING[mode])
+    rec = dict(llm=llm, mode=mode, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
+               clips_ms={}, loop_ms={}, clips_spread={}, loop_spread={}, clips_ms_per_clip={}, loop_ms_per_clip={}, rows_step_ms={})
+    for B in args.batches:
+        clips = [(images, context, sam, x[None], *rest) for x in prompts[:B]]
+        loop = lambda: [model.inference(*c, **kw) for c in clips]        # noqa: E731
+        bat = lambda: model.inference_clips(clips, **kw)                 # noqa: E731
+        tl, tb = [], []
+        for r in range(args.warmup + args.reps):
+            torch.manual_seed(100 + r)
+            a = once(loop)
+            torch.manual_seed(100 + r)
+            b = once(bat)
+            if r >= args.warmup:
+                tl.append(a)
+                tb.append(b)
+        ml, mb = statistics.median(tl), statistics.median(tb)
+        rec["loop_ms"][B], rec["clips_ms"][B] = round(ml, 2), round(mb, 2)
+        rec["loop_spread"][B], rec["clips_spread"][B] = [round(min(tl), 2), round(max(tl), 2)], [round(min(tb), 2), round(max(tb), 2)]
+        rec["loop_ms_per_clip"][B], rec["clips_ms_per_clip"][B] = round(ml / B, 2), round(mb / B, 2)
+        rec["rows_step_ms"][B] = rows_step_ms(model) if B > 1 else None
+    rec["decode_step_ms"] = decode_step_ms(model)
+    del model, sd
+    torch.cuda.empty_cache()
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--llm", nargs="+", default=["llama3-8b", "phi3-mini"], choices=["llama3-8b", "phi3-mini"])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8, 16])
+    ap.add_argument("--reps", type=int, default=3, help="timed repetitions (>= 3 for a median and a spread)")
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--src", type=int, default=1024)
+    ap.add_argument("--max-new-tokens", type=int, default=32)
+    ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
+    ap.add_argument("--sample", nargs="*", default=None, choices=["k50", "k0"], help="also (or, given alone with --no-greedy, only) the sampled modes")
+    ap.add_argument("--no-greedy", action="store_true")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    torch.set_grad_enabled(False)
+    device = torch.device("cuda", 0)
+    modes = ([] if args.no_greedy else ["greedy"]) + list(args.sample or [])
+    for llm in args.llm:
+        for mode in modes:
+            line = json.dumps(run(llm, mode, args, device))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

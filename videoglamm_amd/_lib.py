@@ -71,6 +71,7 @@ def _sig(lib):
         "vg_decode_attention_rows": ([P, L, P, P, I, P, P, L, I, I, P, P, P, I, I, I, I, I, F, P, I, P, L, I, I, P], c_int),
         "vg_sample_workspace_ints": ([], c_int),
         "vg_sample_partial": ([P, I, P, P, P, P, P, P, P], c_int),
+        "vg_sample_partial_rows": ([P, L, I, I, P, P, P, P, P, P, P], c_int),
         "vg_sample_survivors": ([P, I, P, P, P, I, P, P], c_int),
         "vg_sample_philox": ([P, P, I, P, P], c_int),
         "vg_mlp3_grouped": ([P, L, L, P, P, P, P, P, P, P, L, L, I, I, I, I, I, I, ctypes.c_uint, P], c_int),

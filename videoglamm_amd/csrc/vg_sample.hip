@@ -13,7 +13,8 @@
 // in uint64, so histogram sums are integer atomics whose result does not depend on their order: the same seed, row and parameters give the
 // same token on every run.  The truncation costs < 2^-40 of the largest probability per entry (< 1.2e-7 summed over 128 256 entries).
 //
-// Two routes, each ONE launch:
+// Two routes, each ONE launch (vg_sample_partial_rows: the same two routes with a row grid dimension, B rows of a batched step in one launch,
+// row r bit-identical to the single-row launch on row r):
 //   fast (1 <= k <= 64, n <= 64 * 2048): up to 64 workgroups of 256 threads (argmax_stage1's shape); each keeps the top 64 of its slice
 //     (a radix select over the slice held in registers) in a workspace; the last workgroup to arrive (self-resetting ticket) merges the
 //     <= 4096 candidates in LDS and finishes the chain there.  A slice that had to drop entries tied at its 64th value while that value is
@@ -342,6 +343,20 @@ __global__ __launch_bounds__(SB) void sample_kernel(const float* __restrict__ x,
   sample_general<SB>(s, x, n, prm, o);
 }
 
+// row r of a batched step: its own step word, uniform, accumulator and token slot (the survivor dump is single-row only)
+__device__ __forceinline__ SampleOut out_row(const SampleOut& o, int r) {
+  return SampleOut{o.step + r, o.u_override ? o.u_override + r : nullptr, o.acc ? o.acc + r : nullptr, o.tok ? o.tok + r : nullptr,
+                   nullptr, nullptr, 0, nullptr};
+}
+
+// the general route for B rows in one launch: workgroup r runs sample_kernel's body on row r (x + r * ldx) with parameter block prm[r]
+__global__ __launch_bounds__(SB) void sample_rows_kernel(const float* __restrict__ x, long long ldx, int n, const SampleParams* __restrict__ prm,
+                                                         SampleOut o) {
+  __shared__ SampleLds s;
+  const int r = blockIdx.y;
+  sample_general<SB>(s, x + (long long)r * ldx, n, prm + r, out_row(o, r));
+}
+
 // The fast route.  ws: FAST_WS_INTS int32, zero-filled once (the ticket resets itself): [64][64] float y, [64][64] int index, [64][4] meta
 // (stored count, the slice's 64th key Kloc, dropped-ties flag), ticket.
 constexpr int FT = 256;            // threads per workgroup
@@ -349,9 +364,9 @@ constexpr int FPT = 8;             // entries per thread: a slice is at most 204
 constexpr int FMAXWG = 64;
 constexpr int FAST_WS_INTS = 2 * FMAXWG * 64 + FMAXWG * 4 + 64;
 
-__global__ __launch_bounds__(FT) void sample_fast_kernel(const float* __restrict__ x, int n, const SampleParams* __restrict__ prm, SampleOut o,
-                                                         int* __restrict__ ws, int nb) {
-  __shared__ SampleLds s;
+// the body of a fast-route workgroup: slice blockIdx.x of nb of the row x[n], workspace ws (the row's own)
+__device__ __forceinline__ void sample_fast(SampleLds& s, const float* __restrict__ x, int n, const SampleParams* __restrict__ prm, const SampleOut& o,
+                                            int* __restrict__ ws, int nb) {
   const int tid = threadIdx.x, b = blockIdx.x;
   float* wy = (float*)ws;
   int* wi = ws + FMAXWG * 64;
@@ -534,6 +549,22 @@ __global__ __launch_bounds__(FT) void sample_fast_kernel(const float* __restrict
   }
 }
 
+__global__ __launch_bounds__(FT) void sample_fast_kernel(const float* __restrict__ x, int n, const SampleParams* __restrict__ prm, SampleOut o,
+                                                         int* __restrict__ ws, int nb) {
+  __shared__ SampleLds s;
+  sample_fast(s, x, n, prm, o, ws, nb);
+}
+
+// the fast route for B rows in one launch: grid (nb, B); the workgroups of row r = blockIdx.y work in the row's own slice of the workspace
+// (candidates, meta and a self-resetting ticket per row), so a row's last arriver merges that row alone and a tie overflow or a k outside
+// 1..64 sends only that row to the general route
+__global__ __launch_bounds__(FT) void sample_fast_rows_kernel(const float* __restrict__ x, long long ldx, int n, const SampleParams* __restrict__ prm,
+                                                              SampleOut o, int* __restrict__ ws, int nb) {
+  __shared__ SampleLds s;
+  const int r = blockIdx.y;
+  sample_fast(s, x + (long long)r * ldx, n, prm + r, out_row(o, r), ws + (long long)r * FAST_WS_INTS, nb);
+}
+
 __global__ __launch_bounds__(256) void philox_kernel(const unsigned long long* __restrict__ seeds, const int* __restrict__ steps, int n,
                                                      uint32_t* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -555,6 +586,23 @@ extern "C" int vg_sample_partial(const float* x, int n, const void* params, cons
     sample_fast_kernel<<<nb, FT, 0, (hipStream_t)stream>>>(x, n, (const SampleParams*)params, o, fast_ws, nb);
   } else {
     sample_kernel<<<1, SB, 0, (hipStream_t)stream>>>(x, n, (const SampleParams*)params, o);
+  }
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_sample_partial_rows(const float* x, int64_t ldx, int n, int B, const void* params, const int* step, const float* u_override,
+                                      uint64_t* acc, int64_t* tok, int* fast_ws, vg_stream_t stream) {
+  VG_CHECK(x && params && step && (acc || tok) && n > 0 && n < (1 << 22) && B >= 1 && B <= 65535 && ldx >= n, VG_ERR_ARG,
+           "vg_sample_partial_rows: bad args");
+  VG_CHECK(!fast_ws || n <= FMAXWG * FT * FPT, VG_ERR_ARG, "vg_sample_partial_rows: the fast route takes rows of at most 131072 entries");
+  const SampleOut o{step, u_override, (unsigned long long*)acc, tok, nullptr, nullptr, 0, nullptr};
+  if (fast_ws) {
+    int nb = (n + FT * FPT - 1) / (FT * FPT);
+    nb = nb < 1 ? 1 : nb;
+    sample_fast_rows_kernel<<<dim3(nb, B), FT, 0, (hipStream_t)stream>>>(x, (long long)ldx, n, (const SampleParams*)params, o, fast_ws, nb);
+  } else {
+    sample_rows_kernel<<<dim3(1, B), SB, 0, (hipStream_t)stream>>>(x, (long long)ldx, n, (const SampleParams*)params, o);
   }
   VG_LAUNCH_CHECK();
   return VG_OK;

@@ -591,3 +591,83 @@ class VideoGLaMMForCausalLM:
         stage_mark(self.stages, "propagation" if video else "mask_decode")
         # objects [a, a + n) are prompt b's, renumbered from 0
         return out, [self._segments(host[:, a:a + n]) if n else {} for a, n in zip(starts, counts)]
+
+    # ------------------------------------------------------------------ several clips, one prompt each
+    def inference_clips(self, clips, max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
+                        generator=None):
+        """B clips, one prompt each -> a list whose entry b is what inference(*clips[b], max_new_tokens, use_sam2_video_branch, ...) returns:
+        (output ids [1, L_b + G_b], [{frame: {obj: mask}}]), the same ids and the same masks pixel for pixel.  clips[b]: the six per-clip arguments
+        of inference() (images, context_images, images_for_sam, input_ids, resize_list, original_size_list) as a tuple or a dict.
+        Every clip runs its own towers, Hiera and whole-prompt prefill; the clips of a group (up to 16) then decode together, one row per clip in
+        one batched step per token, wherever prompts.batched_route allows it (VG_CLIPS_BATCHED=0: one clip after another), and the mask decode runs
+        per clip after the group's decode.  A clip's Hiera features are kept until then (8.4 MB per 1024^2 frame in bf16).  Sampling draws one seed
+        per clip from `generator`, in list order: torch.manual_seed(n) before this call gives what it gives before the B inference() calls.
+        A clip without a [SEG] behaves as in inference(): [{}] on the video branch, the reference's AttributeError on the framewise one."""
+        from .clips import as_clip, groups
+        if self.comm is not None and self.comm.world > 1:
+            raise NotImplementedError("inference_clips() runs on one GPU: call inference() per clip on a multi-GPU model")
+        clips = [as_clip(c, b) for b, c in enumerate(clips)]
+        if not clips:
+            raise NotImplementedError("inference_clips() needs at least one clip")
+        if self.capture is not None or self.stages is not None:
+            raise NotImplementedError("model.capture / model.stages are diagnostics of inference() and inference_prompts(): unset them for "
+                                      "inference_clips(), or call inference() per clip")
+        if use_sam2_video_branch and not self.config.use_sam2:
+            raise ValueError("use_sam2_video_branch is True, but model is not configured to use SAM2")
+        for b, (images, context_images, images_for_sam, input_ids, _, original_size_list) in enumerate(clips):
+            if len(images) != 1 or getattr(input_ids, "ndim", 0) != 2 or input_ids.shape[0] != 1:      # batch size is 1 per clip (VideoGLaMM.py:252-253)
+                raise ValueError(f"clips[{b}]: one clip per entry (images of length 1, input_ids [1, L]), as inference() takes them")
+        if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
+            torch.cuda.set_device(self.device)
+        samplings = [resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator) for _ in clips]
+        out = []
+        # generate_clips groups by 16 itself; the groups are cut here as well so that the Hiera features (and SAM frames) held until the mask
+        # decode are those of one group, never of the whole list
+        for g0, g1 in groups(len(clips)):
+            out += self._clips_group(clips[g0:g1], max_new_tokens, use_sam2_video_branch, samplings[g0:g1])
+        return out
+
+    def _clips_group(self, clips, max_new_tokens, video, samplings):
+        from .clips import generate_clips
+        mode = os.environ.get("VG_HIERA_START", "first")
+        sams, feats, joins = {}, {}, {}
+
+        def start(b):
+            # Hiera + FPN of clip b on the side stream, as _text_and_hiera starts it; its features live in buffers of their own until the clip's
+            # mask decode (the video branch's replay buffers, SAM2.video_static_feats, are shared by every clip of a length: they would alias
+            # between the clips of a group, so this entry point takes video_branch_graphed's staged-input form)
+            sams[b] = clips[b][2][0].to(self.device)
+            if mode == "serial":
+                feats[b], joins[b] = self.sam2.hiera_frames(sams[b]), (lambda: None)
+            else:
+                feats[b], joins[b] = self._hiera_async(sams[b])
+
+        text = []
+        for images, context_images, _, input_ids, _, _ in clips:
+            ctx = context_images[0] if context_images is not None else None
+            text.append((images[0].to(self.device), None if ctx is None else ctx.to(self.device), input_ids[0].cpu()))
+        first = mode in ("first", "serial")
+        res = generate_clips(self.P, self._live_cfg(), self.towers, text, max_new_tokens, self._eos(), token_hook=self.token_hook,
+                             samplings=samplings, before_clip=start if first else None, after_prefill=None if first else start)
+        out = []
+        for b, ((out_ids, emb), clip) in enumerate(zip(res, clips)):
+            joins[b]()
+            out.append((out_ids.unsqueeze(0), self._clip_masks(sams.pop(b), emb, feats.pop(b), tuple(clip[5][0]), video)))
+        return out
+
+    def _clip_masks(self, sam, emb, feats, hw, video):
+        """the single-GPU mask decode of inference_video_branch / inference_framewise for one clip (capture unset)"""
+        if emb.shape[0] == 0:
+            if video:
+                return [{}]
+            # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
+            raise AttributeError("'tuple' object has no attribute 'shape'")
+        fast = self._fast_masks()
+        if video:
+            if self.device.type == "cuda" and os.environ.get("VG_VIDEO_GRAPH", "1") == "1":
+                res = self.sam2.video_branch_graphed(sam, emb, hw, feats, as_masks=fast)
+            else:
+                res = self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=fast)
+        else:
+            res = self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=fast)[0]
+        return [self._segments(self._to_host(res if fast else self._binarize(res)))]

@@ -843,6 +843,28 @@ def sample_partial(x, params_dev, step_dev, acc=None, tok=None, u_override=None,
     _lib.check(rc, "vg_sample_partial")
 
 
+def sample_workspace_rows(B, device):
+    """B fast-route workspaces in one tensor [B, vg_sample_workspace_ints()] (zero-filled): row b of sample_partial_rows works in slice b"""
+    return torch.zeros(int(B), int(_lib.load().vg_sample_workspace_ints()), dtype=torch.int32, device=device)
+
+
+def sample_partial_rows(logits, params, step, acc=None, tok=None, u_override=None, fast_ws=None):
+    """sample_partial on every row of logits [B, V] (fp32, rows contiguous) in one launch (vg_sample_partial_rows): row b with its parameter
+    block params[b] (int32 [B, 6]), step word step[b] and, when given, uniform u_override[b]; acc / tok int64 [B].  Row b is bit-identical to
+    sample_partial on row b alone.  fast_ws (sample_workspace_rows(B)): the multi-workgroup route, a workspace per row; None: the general route."""
+    lib = _lib.load()
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]
+    B, n = logits.shape
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() >= 6 * B and params.shape[-1] == 6
+    assert step.dtype == torch.int32 and step.is_contiguous() and step.numel() >= B
+    assert acc is not None or tok is not None
+    assert all(t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= B) for t in (acc, tok))
+    assert u_override is None or (u_override.dtype == torch.float32 and u_override.is_contiguous() and u_override.numel() >= B)
+    assert fast_ws is None or (fast_ws.dtype == torch.int32 and fast_ws.is_contiguous() and fast_ws.numel() >= B * lib.vg_sample_workspace_ints())
+    rc = lib.vg_sample_partial_rows(_p(logits), logits.stride(0), n, B, _p(params), _p(step), _p(u_override), _p(acc), _p(tok), _p(fast_ws), _stream())
+    _lib.check(rc, "vg_sample_partial_rows")
+
+
 def sample_survivors(x, params_dev):
     """the entries the warpers keep for one fp32 logits row (vg_sample_survivors) -> (indices int64, probabilities fp32), ascending index."""
     lib = _lib.load()

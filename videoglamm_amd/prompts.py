@@ -33,16 +33,17 @@ def sampling_route(sampling, vocab):
     return "sample_fast" if ops.sample_fast_route(int(sampling["k"]), vocab) else "sample"
 
 
-def batched_route(B, rope_path, decode_weights, chain, routes, env, attn_rows=False, w8_rows=False, w4_rows=False):
+def batched_route(B, rope_path, decode_weights, chain, routes, env, attn_rows=False, w8_rows=False, w4_rows=False, switch="VG_PROMPTS_BATCHED"):
     """True when a group of B prompts decodes in one batched step (RowsDecode) instead of one after another.  rope_path: the decoder runs the
     bf16 head_dim-128 rope step (LlamaDecoder.rope_path; B-row kernels cover the shape); attn_rows: the decoder runs the decode_attention step
     (Phi-3-mini width) and the B-row kernels cover its shape (ops.decode_step_rows_supported); decode_weights: cfg["decode_weights"] ("fp8" takes
     the batched step only with w8_rows: the B-row fp8 GEMV covers this decoder's MLP and lm_head row lengths; "mxfp4" only with w4_rows: the B-row MXFP4 GEMV covers the MLP's row lengths and the B-row fp8 GEMV the lm_head's;
     model.inference_prompts() reaches this route for an mxfp4 model with shared=True only); chain: VG_DECODE_CHAIN roles; routes: the set of the prompts' sampling routes; env: the environment (VG_PROMPTS_BATCHED=0 forces the sequential loop;
-    VG_DECODE_AHEAD=1 keeps it too).  Pure: no device work."""
+    VG_DECODE_AHEAD=1 keeps it too); switch: the environment variable whose value "0" forces the sequential loop (clips.generate_clips passes
+    VG_CLIPS_BATCHED).  Pure: no device work."""
     return (B >= 2 and B <= BUCKETS[-1] and (bool(rope_path) or bool(attn_rows)) and (decode_weights != "fp8" or bool(w8_rows)) and (decode_weights != "mxfp4" or bool(w4_rows))
             and not chain and len(set(routes)) == 1
-            and env.get("VG_PROMPTS_BATCHED", "1") != "0" and env.get("VG_DECODE_AHEAD", "0") != "1")
+            and env.get(switch, "1") != "0" and env.get("VG_DECODE_AHEAD", "0") != "1")
 
 
 def slot_layout(P, kw, need):
@@ -105,16 +106,8 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
         after_prefix()
     vocab = params.t("lm_head.weight").shape[0]
     routes = [sampling_route(sp, vocab) for sp in samplings]
-    rope_rows = dec.rope_path and ops.decode_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype)
-    attn_rows = (not dec.rope_path and dec.fused_decode and params.device.type == "cuda"
-                 and ops.decode_step_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype))
-    # fp8 decode weights: gate|up and the lm_head run at K = hidden, down at K = ffn
-    w8_rows = dec.w8 and ops.decode_gemv_w8_rows_supported(dec.D) and ops.decode_gemv_w8_rows_supported(_ffn(params))
-    # mxfp4 decode weights: gate|up at K = hidden and down at K = ffn on the B-row MXFP4 GEMV, the lm_head (fp8) at K = hidden
-    w4_rows = (dec.w4 and ops.decode_gemv_w4_rows_supported(dec.D) and ops.decode_gemv_w4_rows_supported(_ffn(params))
-               and ops.decode_gemv_w8_rows_supported(dec.D))
-    batched = max_new_tokens > 1 and batched_route(B, rope_rows, cfg["llm"].get("decode_weights"), dec.chain_roles, routes, os.environ,
-                                                   attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=w4_rows)
+    rope_rows, cover = rows_cover(params, dec)
+    batched = max_new_tokens > 1 and batched_route(B, rope_rows, cfg["llm"].get("decode_weights"), dec.chain_roles, routes, os.environ, **cover)
     rows = None
     if batched:
         row0, n_bound = slot_layout(P, dec.kpw2 if dec.rope_path else RowsDecode.ATTN_KW, need)
@@ -165,6 +158,19 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
     if not embs:
         return out, torch.empty(0, 256, dtype=params.dtype, device=params.device), counts
     return out, torch.cat(embs), counts
+
+
+def rows_cover(params, dec):
+    """(rope_rows, dict(attn_rows, w8_rows, w4_rows)): which forms of the B-row step cover this decoder — batched_route's shape arguments"""
+    rope_rows = dec.rope_path and ops.decode_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype)
+    attn_rows = (not dec.rope_path and dec.fused_decode and params.device.type == "cuda"
+                 and ops.decode_step_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype))
+    # fp8 decode weights: gate|up and the lm_head run at K = hidden, down at K = ffn
+    w8_rows = dec.w8 and ops.decode_gemv_w8_rows_supported(dec.D) and ops.decode_gemv_w8_rows_supported(_ffn(params))
+    # mxfp4 decode weights: gate|up at K = hidden and down at K = ffn on the B-row MXFP4 GEMV, the lm_head (fp8) at K = hidden
+    w4_rows = (dec.w4 and ops.decode_gemv_w4_rows_supported(dec.D) and ops.decode_gemv_w4_rows_supported(_ffn(params))
+               and ops.decode_gemv_w8_rows_supported(dec.D))
+    return rope_rows, dict(attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=w4_rows)
 
 
 def _ffn(params):

@@ -612,9 +612,8 @@ class RowsDecode:
         if self.route == "greedy":
             ops.argmax_partial_rows(logits, self.acc)
         else:
-            for b in range(self.B):     # vg_sample per row: its own parameter block, step counter and accumulator
-                ops.sample_partial(logits[b], self.samp_params[b], self.step[b:b + 1], acc=self.acc[b:b + 1],
-                                   fast_ws=self.samp_ws if self.route == "sample_fast" else None)
+            # vg_sample for the B rows in one launch: every row its own parameter block, step counter, accumulator and (fast route) workspace
+            ops.sample_partial_rows(logits, self.samp_params, self.step, acc=self.acc, fast_ws=self.samp_ws if self.route == "sample_fast" else None)
         ops.decode_step_end_rows(self.acc, self.tok, self.pos, self.step, h, self.hid, forced=self.forced, hist=self.hist, raw=self.raw,
                                  hid_row0=self.row0)
 
@@ -628,7 +627,7 @@ class RowsDecode:
         if max(self.host_pos) >= self.n_bound:
             raise ValueError(f"RowsDecode: a row at position {max(self.host_pos)} is past the slots' bound {self.n_bound}")
         if self.route != "greedy" and self.samp_ws is None:
-            self.samp_ws = ops.sample_workspace(self.dec.P.device)
+            self.samp_ws = ops.sample_workspace_rows(self.B, self.dec.P.device)
         self.steps += 1
         self.host_pos = [p + 1 for p in self.host_pos]
         if not self.dec.use_graph:

@@ -244,6 +244,17 @@ int vg_decode_advance(int64_t* tok, int* pos, int* step, const int64_t* forced, 
 int vg_decode_rows_supported(int H, int Hkv, int D, int hidden, int inter, int dtype);
 int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
                         const void* R, int64_t ldr, int N, int K, int B, int glu, int dtype, vg_stream_t stream);
+/* The B-row projections of the decode mode decode_gemv = "mfma" (DESIGN.md section 11): y[b] = f(x[b]) . W^T (+ R[b]) on v_mfma_f32_16x16x32_bf16.
+ * Arguments as vg_decode_gemv_rows; x bf16, W bf16 [N or 2N, K] read in place, y / R of out_dtype (VG_BF16 | VG_F32).  B in [1, 16]: the batch is
+ * always one 16-row operand whose rows >= B are zeros, and neither the K walk nor the order of the partial sums depends on B, so row b of a B-row
+ * call is bit-identical to the one-row call on row b, whatever the other rows hold (the single-row step of the mode calls this with B = 1).
+ * Sums: fp32, k ascending inside each of four K slices, the slices added in order.  norm_w: RMSNorm prologue with vg_decode_gemv's roundings
+ * (equal to vg_rmsnorm followed by the plain call), K <= 4096 only, VG_ERR_UNSUPPORTED beyond.  glu: SwiGLU epilogue of vg_decode_gemv.
+ * K one of 3072, 4096, 8192, 14336, any N > 0 (per half when glu; a last tile of fewer than 16 weight rows re-reads row N - 1 and stores nothing
+ * for the missing rows) (vg_decode_gemm_rows_supported(N, K) != 0), VG_ERR_UNSUPPORTED otherwise.  x, W and norm_w 16-byte aligned, ldx / ldw multiples of 8.  No workspace and no communication between workgroups. */
+int vg_decode_gemm_rows_supported(int N, int K);
+int vg_decode_gemm_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
+                        const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream);
 /* vg_decode_gemv_w8 for B rows (the MLP and the lm_head of the batched step with fp8 decode weights): x[b] = x + b * ldx (bf16, K elements),
  * W8 [N or 2N, K] fp8 e4m3 with one fp32 scale per weight row, y[b] = y + b * ldy (out_dtype VG_BF16 | VG_F32), residual R + b * ldr of the output
  * dtype, norm_w / eps and glu as vg_decode_gemv_w8.  Row b is bit-identical to vg_decode_gemv_w8 on row b alone; every weight chunk is read once.

@@ -9,10 +9,13 @@ The two forms alternate inside each repetition; one JSON line per (LLM, mode):
   "rows_step_ms"[B]:  one replayed batched decode step of the bucket B runs in (vlm.RowsDecode with row0 = 0), rows at the clips' positions
   "decode_step_ms":   one replayed single-row decode step (LlamaDecoder.decode_step), ms per token
 --sample k50 / k0: sampled decoding (k 50, p 0.9, T 0.6: the fast route; k 0, p 0.9: the general route), seeded per repetition.
+--decode-gemv valu mfma: the decode mode cfg["llm"]["decode_gemv"]; given both, one model per mode is built on the same weights and
+the modes alternate inside each repetition (loop, clips and the replayed step of one mode, then of the other); one line per mode, with
+"rows_step_spread"[B] / "decode_step_spread" = [min, max] over the repetitions.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 12's table lives in profiles/).
 
     python tools/bench_clips.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8 16] [--reps 3] [--warmup 1] [--branch framewise]
-                                 [--sample k50 k0] [--out FILE]
+                                 [--sample k50 k0] [--decode-gemv valu mfma] [--out FILE]
 """
 import argparse
 import json
@@ -45,7 +48,10 @@ def run(llm, mode, args, device):
     cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
     sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
-    model = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, cfg, torch_dtype=torch.bfloat16, device=device))
+    models = {}
+    for dg in args.decode_gemv:          # one model per decode mode on the same weight tensors
+        c = dict(cfg, llm=dict(cfg["llm"], decode_gemv=dg)) if dg != "valu" else cfg
+        models[dg] = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, c, torch_dtype=torch.bfloat16, device=device))
     g = torch.Generator().manual_seed(1234)
     te, S = 16, cfg["sam2"]["image_size"]
     iv, cl = cfg["iv2"]["img_size"], cfg["clip"]["img_size"]
@@ -57,30 +63,43 @@ def run(llm, mode, args, device):
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
     kw = dict(max_new_tokens=args.max_new_tokens, use_sam2_video_branch=video, **SAMPLING[mode])
-    rec = dict(llm=llm, mode=mode, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
-               clips_ms={}, loop_ms={}, clips_spread={}, loop_spread={}, clips_ms_per_clip={}, loop_ms_per_clip={}, rows_step_ms={})
+    recs = {dg: dict(llm=llm, mode=mode, decode_gemv=dg, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
+                     clips_ms={}, loop_ms={}, clips_spread={}, loop_spread={}, clips_ms_per_clip={}, loop_ms_per_clip={}, rows_step_ms={},
+                     rows_step_spread={}) for dg in models}
+    spread = lambda v: [round(min(v), 4), round(max(v), 4)]              # noqa: E731
     for B in args.batches:
         clips = [(images, context, sam, x[None], *rest) for x in prompts[:B]]
-        loop = lambda: [model.inference(*c, **kw) for c in clips]        # noqa: E731
-        bat = lambda: model.inference_clips(clips, **kw)                 # noqa: E731
-        tl, tb = [], []
+        tl, tb, ts = ({dg: [] for dg in models} for _ in range(3))
         for r in range(args.warmup + args.reps):
-            torch.manual_seed(100 + r)
-            a = once(loop)
-            torch.manual_seed(100 + r)
-            b = once(bat)
-            if r >= args.warmup:
-                tl.append(a)
-                tb.append(b)
-        ml, mb = statistics.median(tl), statistics.median(tb)
-        rec["loop_ms"][B], rec["clips_ms"][B] = round(ml, 2), round(mb, 2)
-        rec["loop_spread"][B], rec["clips_spread"][B] = [round(min(tl), 2), round(max(tl), 2)], [round(min(tb), 2), round(max(tb), 2)]
-        rec["loop_ms_per_clip"][B], rec["clips_ms_per_clip"][B] = round(ml / B, 2), round(mb / B, 2)
-        rec["rows_step_ms"][B] = rows_step_ms(model) if B > 1 else None
-    rec["decode_step_ms"] = decode_step_ms(model)
-    del model, sd
+            for dg, model in models.items():      # the modes alternate inside the repetition
+                torch.manual_seed(100 + r)
+                a = once(lambda: [model.inference(*c, **kw) for c in clips])
+                torch.manual_seed(100 + r)
+                b = once(lambda: model.inference_clips(clips, **kw))
+                st = rows_step_ms(model) if B > 1 else None
+                if r >= args.warmup:
+                    tl[dg].append(a)
+                    tb[dg].append(b)
+                    ts[dg].append(st)
+        for dg, rec in recs.items():
+            ml, mb = statistics.median(tl[dg]), statistics.median(tb[dg])
+            rec["loop_ms"][B], rec["clips_ms"][B] = round(ml, 2), round(mb, 2)
+            rec["loop_spread"][B], rec["clips_spread"][B] = spread(tl[dg]), spread(tb[dg])
+            rec["loop_ms_per_clip"][B], rec["clips_ms_per_clip"][B] = round(ml / B, 2), round(mb / B, 2)
+            live = [v for v in ts[dg] if v is not None]
+            rec["rows_step_ms"][B] = round(statistics.median(live), 4) if live else None
+            rec["rows_step_spread"][B] = spread(live) if live else None
+    td = {dg: [] for dg in models}
+    for r in range(args.reps):
+        for dg, model in models.items():
+            td[dg].append(decode_step_ms(model, tokens=24))
+    for dg, rec in recs.items():
+        live = [v for v in td[dg] if v is not None]
+        rec["decode_step_ms"] = round(statistics.median(live), 4) if live else None
+        rec["decode_step_spread"] = spread(live) if live else None
+    del models, sd
     torch.cuda.empty_cache()
-    return rec
+    return list(recs.values())
 
 
 def main():
@@ -95,6 +114,8 @@ def main():
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
     ap.add_argument("--sample", nargs="*", default=None, choices=["k50", "k0"], help="also (or, given alone with --no-greedy, only) the sampled modes")
     ap.add_argument("--no-greedy", action="store_true")
+    ap.add_argument("--decode-gemv", nargs="+", default=["valu"], choices=["valu", "mfma"],
+                    help="cfg['llm']['decode_gemv']; both: the modes alternate inside each repetition, one line per mode")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
@@ -102,11 +123,12 @@ def main():
     modes = ([] if args.no_greedy else ["greedy"]) + list(args.sample or [])
     for llm in args.llm:
         for mode in modes:
-            line = json.dumps(run(llm, mode, args, device))
-            print(line, flush=True)
-            if args.out:
-                with open(args.out, "a") as f:
-                    f.write(line + "\n")
+            for rec in run(llm, mode, args, device):
+                line = json.dumps(rec)
+                print(line, flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(line + "\n")
 
 
 if __name__ == "__main__":

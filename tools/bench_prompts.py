@@ -12,10 +12,13 @@ differ in their 30 question ids.  One JSON line per LLM:
 --ab also times inference_prompts() with VG_PROMPTS_BATCHED=0 ("prompts_seq_ms"[B]: the prompts decoded one after another).
 --shared passes shared=True: the shared route for every model.  An mxfp4 model takes it only then (its default is one inference() per prompt, which
 is what "sequential_ms" times), so --decode-weights mxfp4 --shared --ab compares the batched MXFP4 step with the sequential loop on that route.
+--decode-gemv mfma: the decode mode cfg["llm"]["decode_gemv"] = "mfma" (bf16 decode weights only), written into each line; given both values, one
+line per mode, each LLM's two runs back to back.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 
     python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise]
-                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--shared] [--ab] [--out FILE]
+                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--shared] [--ab] [--decode-gemv valu mfma]
+                                   [--out FILE]
 """
 import argparse
 import json
@@ -79,9 +82,11 @@ def rows_step_ms(model, tokens=32):
     return round(e0.elapsed_time(e1) / (tokens - 1), 4)
 
 
-def run(llm, args, device):
+def run(llm, args, device, decode_gemv="valu"):
     cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
+    if decode_gemv != "valu":
+        cfg["llm"] = dict(cfg["llm"], decode_gemv=decode_gemv)
     if args.decode_weights in ("fp8", "mxfp4"):
         cfg["llm"] = dict(cfg["llm"], decode_weights=args.decode_weights)
     if args.prefill == "fp8":
@@ -98,7 +103,7 @@ def run(llm, args, device):
     prompts = [torch.cat([head, torch.randint(3, cfg["llm"]["vocab"] - 2, (30,), generator=g)]) for _ in range(max(args.batches))]
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
-    rec = dict(llm=llm, decode_weights=args.decode_weights, prefill=args.prefill, branch=args.branch, frames=args.frames,
+    rec = dict(llm=llm, decode_gemv=decode_gemv, decode_weights=args.decode_weights, prefill=args.prefill, branch=args.branch, frames=args.frames,
                max_new_tokens=args.max_new_tokens, shared=args.shared, prompts_ms={}, sequential_ms={}, ratio={},
                rows_step_ms={})
     kw = dict(shared=True) if args.shared else {}
@@ -140,16 +145,18 @@ def main():
     ap.add_argument("--prefill", default="bf16", choices=["bf16", "fp8"], help="fp8: the LLM prefill GEMMs on the fp8 MFMA path, as bench.py --prefill")
     ap.add_argument("--shared", action="store_true", help="call inference_prompts(..., shared=True): the shared route for every model, mxfp4 included")
     ap.add_argument("--ab", action="store_true", help="also time inference_prompts() on the sequential loop (VG_PROMPTS_BATCHED=0)")
+    ap.add_argument("--decode-gemv", nargs="+", default=["valu"], choices=["valu", "mfma"], help="cfg['llm']['decode_gemv']; one line per value")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     device = torch.device("cuda", 0)
     for llm in args.llm:
-        line = json.dumps(run(llm, args, device))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
+        for dg in args.decode_gemv:
+            line = json.dumps(run(llm, args, device, dg))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -56,6 +56,8 @@ def _sig(lib):
         "vg_decode_step_end": ([P, P, P, P, P, I, P, P, I, P, P, I, I, P], c_int),
         "vg_decode_rows_supported": ([I, I, I, I, I, I], c_int),
         "vg_decode_gemv_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
+        "vg_decode_gemm_rows_supported": ([I, I], c_int),
+        "vg_decode_gemm_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_gemv_w8_rows_supported": ([I], c_int),
         "vg_decode_gemv_w8_rows": ([P, L, P, L, P, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_gemv_w4_rows_supported": ([I], c_int),

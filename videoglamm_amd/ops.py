@@ -924,6 +924,31 @@ def decode_gemv_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out=N
     return y
 
 
+def decode_gemm_rows_supported(N, K):
+    """True when the MFMA B-row projection covers a [N, K] weight (vg_decode_gemm_rows_supported: K of 3072 / 4096 / 8192 / 14336, any N)."""
+    return bool(_lib.load().vg_decode_gemm_rows_supported(int(N), int(K)))
+
+
+def decode_gemm_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """The decode projection of the B <= 16 rows of x [B,K] on the matrix pipe (vg_decode_gemm_rows; the mode decode_gemv = "mfma") -> [B,N] of
+    out_dtype (bf16 | fp32).  Row b equals the one-row call on row b bit for bit."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+    N = w.shape[0] // 2 if glu else w.shape[0]
+    od = out.dtype if out is not None else (out_dtype or x.dtype)
+    y = out if out is not None else torch.empty(B, N, dtype=od, device=x.device)
+    assert y.shape == (B, N) and y.stride(1) == 1 and y.dtype == od
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
+        ldr = residual.stride(0)
+    rc = lib.vg_decode_gemm_rows(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)), float(eps),
+                                 _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y), _stream())
+    _lib.check(rc, "vg_decode_gemm_rows")
+    return y
+
+
 def decode_gemv_w8_rows_supported(K):
     """True when the B-row fp8 GEMV has the row length K (vg_decode_gemv_w8_rows_supported: 3072, 4096, 8192, 14336)."""
     return bool(_lib.load().vg_decode_gemv_w8_rows_supported(int(K)))

@@ -163,6 +163,31 @@ class VisionTowers:
         return torch.cat([cf, vf], dim=0)
 
 
+def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, supported):
+    """cfg["llm"]["decode_gemv"]: False for None / "valu" (the decode GEMVs of DESIGN 5d / 11), True for "mfma" (every plain projection of the
+    single-row and the B-row step on vg_decode_gemm_rows) — or a ValueError that names why this decoder cannot take the mode.
+    decode_weights: cfg["llm"]["decode_weights"]; dtype: the model's; env: the environment; step: "rope" (Llama-3 width: q|k|v + RoPE + append
+    stays on its own kernel), "attention" (Phi-3-mini width: the q|k|v GEMV moves too) or None (neither B-row step covers the decoder);
+    projections: the (N, K) of the weights the mode moves; supported: ops.decode_gemm_rows_supported.  Pure: no device work."""
+    if value in (None, "valu"):
+        return False
+    if value != "mfma":
+        raise ValueError(f"cfg['llm']['decode_gemv'] = {value!r}: 'valu' (default) or 'mfma'")
+    if decode_weights in ("fp8", "mxfp4"):
+        raise ValueError(f"decode_gemv = 'mfma' streams the bf16 weights: it does not combine with decode_weights = {decode_weights!r}")
+    if dtype != torch.bfloat16:
+        raise ValueError(f"decode_gemv = 'mfma' needs a bf16 model (v_mfma_f32_16x16x32_bf16), not {dtype}")
+    for knob in ("VG_DECODE_CHAIN", "VG_DECODE_AHEAD"):
+        if env.get(knob, "0") != "0":
+            raise ValueError(f"decode_gemv = 'mfma' does not combine with {knob}={env.get(knob)}")
+    if step not in ("rope", "attention"):
+        raise ValueError("decode_gemv = 'mfma': this decoder takes neither the rope step (Llama-3 width) nor the decode_attention rows step (Phi-3-mini width)")
+    for N, K in projections:
+        if not supported(N, K):
+            raise ValueError(f"decode_gemv = 'mfma': vg_decode_gemm_rows does not cover a [{N}, {K}] projection (uncovered width)")
+    return True
+
+
 class LlamaDecoder:
     """HF LlamaModel / Phi3Model arithmetic (RMSNorm, rotate-half RoPE, GQA attention, SwiGLU) with a KV cache.  Phi-3 (the
     released checkpoint's LLM, R/model/videogpt_plus/model/language_model/phi3.py:29-40) is the same graph with the
@@ -239,6 +264,19 @@ class LlamaDecoder:
         self.rope_path = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
                           and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
         self.kpw2 = int(os.environ.get("VG_DEC2_KPW", "256"))
+        # cfg["decode_gemv"] == "mfma": the plain projections of the decode step (o, gate|up, down, the lm_head; q|k|v too on the decode_attention
+        # step) run on vg_decode_gemm_rows, single-row step and B-row step alike; absent / "valu": the decode GEMVs above
+        step = None
+        if self.rope_path:
+            step = "rope"
+        elif self.fused_decode and dev.type == "cuda" and not self.chain_roles and ops.decode_step_rows_supported(self.H, self.Hkv, self.hd, self.D, ffn, dt):
+            step = "attention"
+        proj = []
+        if c.get("decode_gemv") == "mfma":
+            proj = [(self.D, self.H * self.hd), (ffn, self.D), (self.D, ffn), (params.t("lm_head.weight").shape[0], self.D)]
+            if step == "attention":
+                proj.append(((self.H + 2 * self.Hkv) * self.hd, self.D))
+        self.mfma = decode_gemv_mode(c.get("decode_gemv"), c.get("decode_weights"), dt, os.environ, step, proj, ops.decode_gemm_rows_supported)
         # sampled decoding (vg_sample): None = greedy; else dict(T, k, p, seed), the values held in the device block samp_params that
         # the captured step reads — a new temperature / top-p / top-k / seed is a copy into it, never a re-capture
         self.sampling, self.samp_params, self.samp_ws, self.samp_fast = None, None, None, False
@@ -317,6 +355,7 @@ class LlamaDecoder:
                 self.chain_err = torch.zeros((), dtype=torch.int32, device=x.device)
             self.chain_err.add_(self.chain_flags[:, 1].sum())      # the previous token's gave-up words survive the memset below (generate() checks)
             self.chain_flags.zero_()          # one memset per token: every layer's arrival stripes and go flags
+        gemv = ops.decode_gemm_rows if self.mfma else ops.decode_gemv      # the mode: the B-row kernel with B = 1, the batched step's twin
         if self.rope_path and rope_row:
             ops.decode_advance_(self.pos_dev, 0, rope=(self.cos, self.sin, self.rope_cs))      # the cos / sin row of *pos_dev, once per token (decode_step_begin does it inside a captured step)
         for i in range(c["num_layers"]):
@@ -330,10 +369,10 @@ class LlamaDecoder:
                                         self.pos_dev, self.H, self.Hkv, self.hd)
                 o = ops.decode_attention2(q, self.kc[i], self.vc[i], self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5, self.attn_ws,
                                           window=self.window, keys_per_wg=self.kpw2)
-                x = ops.decode_gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
+                x = gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
                 qkv = None
             else:
-                qkv = ops.decode_gemv(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
+                qkv = gemv(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
             if qkv is None:
                 pass
             elif self.chain_roles:
@@ -351,7 +390,7 @@ class LlamaDecoder:
             else:
                 o = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd,
                                          self.pos_dev, self.hd ** -0.5, self.attn_ws, window=self.window, keys_per_wg=self.kpw)
-                x = ops.decode_gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
+                x = gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
             if self.w8:
                 # fp8 weights + row scales for the MLP (81 % of a layer's bytes) — the attention projections stay bf16: at K = 4096
                 # an fp8 row is a single batch of loads per lane and the per-row reduction eats the gain (10.4 vs 9.1 us measured)
@@ -364,8 +403,8 @@ class LlamaDecoder:
                 x = ops.decode_gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
             else:
                 wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
-                a = ops.decode_gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
-                x = ops.decode_gemv(a, P.w(l + "mlp.down_proj"), residual=x)
+                a = gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
+                x = gemv(a, P.w(l + "mlp.down_proj"), residual=x)
         return ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
 
     def forward(self, x):
@@ -422,6 +461,8 @@ class LlamaDecoder:
         """lm_head + argmax (or, sampling, the warpers + the draw of step *step_dev) of one final-norm row -> tok_dev (device int64[1])."""
         if (self.w8 or self.w4) and hidden_row.shape[0] == 1:
             logits = ops.decode_gemv_w8(hidden_row.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
+        elif self.mfma and hidden_row.shape[0] == 1:
+            logits = ops.decode_gemm_rows(hidden_row.contiguous(), self.P.w("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(hidden_row, self.P.w("lm_head"), out_dtype=torch.float32)
         if self.sampling is not None:
@@ -444,6 +485,8 @@ class LlamaDecoder:
         h = self._layers_decode(x, rope_row=False)
         if self.w8 or self.w4:
             logits = ops.decode_gemv_w8(h.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
+        elif self.mfma:
+            logits = ops.decode_gemm_rows(h.contiguous(), self.P.w("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(h, self.P.w("lm_head"), out_dtype=torch.float32)
         if self.sampling is not None:
@@ -507,7 +550,8 @@ class RowsDecode:
     Two forms of the step, as the decoder's single-row step: the rope path (bf16 head_dim 128: q|k|v + RoPE + append, then vg_decode_attention2_rows;
     kw = dec.kpw2) and the decode_attention path (Phi-3-mini width: q|k|v GEMV, then RoPE + append + attention in vg_decode_attention_rows, whose
     rows pick 64 or 128 keys per workgroup on the device from their own position and dec.kpw_min; kw = ATTN_KW).
-    The projections follow the decoder's decode weights: bf16 (vg_decode_gemv_rows), fp8 (the MLP and the lm_head on vg_decode_gemv_w8_rows) or
+    The projections follow the decoder's decode weights: bf16 (vg_decode_gemv_rows; with cfg["decode_gemv"] = "mfma" vg_decode_gemm_rows, the
+    lm_head included, which is also what the decoder's single-row step then runs), fp8 (the MLP and the lm_head on vg_decode_gemv_w8_rows) or
     mxfp4 (the MLP on vg_decode_gemv_w4_rows, the lm_head on vg_decode_gemv_w8_rows); the attention projections are bf16 in all three.
     The step is captured once per sampling route ("greedy" / "sample_fast" / "sample") into a HIP graph; a new seed or temperature is a copy into
     samp_params.  Rows past the live prompts (bucket padding) and retired rows keep computing into their own slots; their tokens are ignored."""
@@ -572,13 +616,14 @@ class RowsDecode:
 
     def _step(self):
         d, P, c = self.dec, self.dec.P, self.dec.c
+        gemv = ops.decode_gemm_rows if d.mfma else ops.decode_gemv_rows      # decode_gemv = "mfma": the kernel of the decoder's single-row step
         x = ops.decode_step_begin_rows(self.tok, P.t("model.embed_tokens.weight"), self.pos,
                                        rope=None if self.attn_rows else (d.cos, d.sin, self.rope_cs))
         for i in range(c["num_layers"]):
             l = f"model.layers.{i}."
             wqkv, _ = P.fused([l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"], stored=l + "self_attn.qkv_proj")
             if self.attn_rows:
-                qkv = ops.decode_gemv_rows(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
+                qkv = gemv(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
                 o = ops.decode_attention_rows(qkv, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.cos, d.sin, d.H, d.Hkv, d.hd, self.pos,
                                               self.n_bound, d.hd ** -0.5, self.attn_ws, window=d.window, kpw_min=d.kpw_min)
             else:
@@ -586,7 +631,7 @@ class RowsDecode:
                                              self.rope_cs, self.pos, d.H, d.Hkv, d.hd)
                 o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
                                                d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
-            x = ops.decode_gemv_rows(o, P.w(l + "self_attn.o_proj"), residual=x)
+            x = gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
             gu_names = [l + "mlp.gate_proj", l + "mlp.up_proj"]
             if d.w8:
                 # fp8 decode weights: the MLP and (below) the lm_head on the B-row fp8 GEMV, the operands LlamaDecoder._layers_decode picks; the
@@ -602,11 +647,13 @@ class RowsDecode:
                 x = ops.decode_gemv_w4_rows(a, P.fp4(l + "mlp.down_proj"), residual=x)
             else:
                 wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
-                a = ops.decode_gemv_rows(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
-                x = ops.decode_gemv_rows(a, P.w(l + "mlp.down_proj"), residual=x)
+                a = gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
+                x = gemv(a, P.w(l + "mlp.down_proj"), residual=x)
         h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
         if d.w8 or d.w4:
             logits = ops.decode_gemv_w8_rows(h, *P.fp8("lm_head"), out_dtype=torch.float32)
+        elif d.mfma:
+            logits = ops.decode_gemm_rows(h, P.w("lm_head"), out_dtype=torch.float32)
         else:
             logits = ops.linear(h, P.w("lm_head"), out_dtype=torch.float32)
         if self.route == "greedy":

@@ -255,6 +255,32 @@ int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, 
 int vg_decode_gemm_rows_supported(int N, int K);
 int vg_decode_gemm_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
                         const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream);
+/* vg_decode_gemm_rows on quantised weights (the decode mode decode_gemv = "mfma_q", DESIGN.md sections 8 and 11): the same walk on
+ * v_mfma_f32_16x16x32_bf16, the weight bytes converted to bf16 operand registers on the way (v_cvt_scalef32_pk_bf16_fp8 / _fp4: exact), so the
+ * VALU work per weight is half an instruction whatever B is.  The operands are those of vg_decode_gemv_w8_rows / vg_decode_gemv_w4_rows:
+ *   W8 [N or 2N, K] OCP e4m3 with one fp32 scale per weight row: converted with scale 1.0, wscale[n] multiplies the fp32 total in the epilogue
+ *     (before the gate / up rounding of the glu form), as vg_decode_gemv_w8; ldw a multiple of 16, >= K.
+ *   W4: the PACKED MXFP4 rows of vg_decode_gemv_w4 read in place (row n at W4 + n * ldw_bytes = a head of 64 * SPL scale bytes, then K / 2 code
+ *     bytes; ldw_bytes a multiple of 16 that covers the row).  The block scale 2^(s - 127) goes into the conversion; a lane's 16-byte load is one
+ *     scale block.  A scale byte 0 means the block is EXACTLY zero, whatever its codes hold (the kernel converts +0 codes in their place: the
+ *     conversion instruction reads only the exponent field of the float s << 23, so 0.0f alone would act as 2^-127).
+ *     The heads of a workgroup's rows are read once, ahead of the walk, with 16-byte loads.
+ * Everything else is vg_decode_gemm_rows' contract: x bf16, y / R of out_dtype (VG_BF16 | VG_F32); B in [1, 16], the batch always one 16-row
+ * operand whose rows >= B are zeros; K one of 3072, 4096, 8192, 14336 and any N > 0 (per half when glu; a ragged last tile re-reads row N - 1 and
+ * stores nothing for the missing rows) (vg_decode_gemm_w8_rows_supported / _w4_rows_supported(N, K) != 0), VG_ERR_UNSUPPORTED otherwise; the
+ * norm form at K <= 4096 only (VG_ERR_UNSUPPORTED beyond), equal to vg_rmsnorm followed by the plain call; x, W and norm_w 16-byte aligned,
+ * ldx a multiple of 8, VG_ERR_ARG otherwise.  No workspace, no communication between workgroups.
+ * Row b of a B-row call is bit-identical to the one-row call on row b, whatever the other rows hold, +-Inf / NaN included.  Sums are fp32, k
+ * ascending inside each of four K slices in the kernel's fixed k order (vg_decode_mfma.hip), the slices added in order ((s0 + s1) + s2) + s3;
+ * nothing depends on B.  Roundings: the epilogue of vg_decode_gemv (gate / up / silu to bf16, residual in the output dtype, one output rounding).
+ * NOT bit-identical to vg_decode_gemv_w8_rows / _w4_rows: the products are the same exact values, summed in another order. */
+int vg_decode_gemm_w8_rows_supported(int N, int K);
+int vg_decode_gemm_w8_rows(const void* x, int64_t ldx, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, int64_t ldy,
+                           const float* norm_w, float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype,
+                           vg_stream_t stream);
+int vg_decode_gemm_w4_rows_supported(int N, int K);
+int vg_decode_gemm_w4_rows(const void* x, int64_t ldx, const uint8_t* W4, int64_t ldw_bytes, void* y, int64_t ldy, const float* norm_w, float eps,
+                           const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream);
 /* vg_decode_gemv_w8 for B rows (the MLP and the lm_head of the batched step with fp8 decode weights): x[b] = x + b * ldx (bf16, K elements),
  * W8 [N or 2N, K] fp8 e4m3 with one fp32 scale per weight row, y[b] = y + b * ldy (out_dtype VG_BF16 | VG_F32), residual R + b * ldr of the output
  * dtype, norm_w / eps and glu as vg_decode_gemv_w8.  Row b is bit-identical to vg_decode_gemv_w8 on row b alone; every weight chunk is read once.

@@ -11,11 +11,15 @@ The two forms alternate inside each repetition; one JSON line per (LLM, mode):
 --sample k50 / k0: sampled decoding (k 50, p 0.9, T 0.6: the fast route; k 0, p 0.9: the general route), seeded per repetition.
 --decode-gemv valu mfma: the decode mode cfg["llm"]["decode_gemv"]; given both, one model per mode is built on the same weights and
 the modes alternate inside each repetition (loop, clips and the replayed step of one mode, then of the other); one line per mode, with
-"rows_step_spread"[B] / "decode_step_spread" = [min, max] over the repetitions.
+"rows_step_spread"[B] / "decode_step_spread" = [min, max] over the repetitions.  mfma_q is the mode of the fp8 / mxfp4 decode weights.
+--decode-weights bf16 fp8 mxfp4: cfg["llm"]["decode_weights"]; every valid (decode_gemv, decode_weights) pair is one model and one line
+("decode_weights" in the record), all alternating inside each repetition; an invalid pair (mfma with fp8 / mxfp4, mfma_q with bf16) is skipped
+with a printed line.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 12's table lives in profiles/).
 
     python tools/bench_clips.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8 16] [--reps 3] [--warmup 1] [--branch framewise]
-                                 [--sample k50 k0] [--decode-gemv valu mfma] [--out FILE]
+                                 [--sample k50 k0] [--decode-gemv valu mfma mfma_q] [--decode-weights bf16 fp8 mxfp4]
+                                 [--out FILE]
 """
 import argparse
 import json
@@ -44,14 +48,23 @@ def once(fn):
     return (time.perf_counter() - t) * 1000.0
 
 
+def pairs(args):
+    """the valid (decode_gemv, decode_weights) pairs of the two option lists: mfma streams bf16 weights, mfma_q fp8 / mxfp4 (vlm.decode_gemv_mode)"""
+    return [(dg, dw) for dw in args.decode_weights for dg in args.decode_gemv
+            if not (dg == "mfma" and dw != "bf16") and not (dg == "mfma_q" and dw == "bf16")]
+
+
 def run(llm, mode, args, device):
     cfg = synth.videoglamm_llama3_8b() if llm == "llama3-8b" else synth.videoglamm_phi3_mini()
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
     sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
     models = {}
-    for dg in args.decode_gemv:          # one model per decode mode on the same weight tensors
-        c = dict(cfg, llm=dict(cfg["llm"], decode_gemv=dg)) if dg != "valu" else cfg
-        models[dg] = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, c, torch_dtype=torch.bfloat16, device=device))
+    for dg, dw in pairs(args):           # one model per (decode mode, decode weights) on the same weight tensors
+        extra = dict(decode_gemv=dg) if dg != "valu" else {}
+        if dw != "bf16":
+            extra["decode_weights"] = dw
+        c = dict(cfg, llm=dict(cfg["llm"], **extra)) if extra else cfg
+        models[(dg, dw)] = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, c, torch_dtype=torch.bfloat16, device=device))
     g = torch.Generator().manual_seed(1234)
     te, S = 16, cfg["sam2"]["image_size"]
     iv, cl = cfg["iv2"]["img_size"], cfg["clip"]["img_size"]
@@ -63,7 +76,7 @@ def run(llm, mode, args, device):
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
     kw = dict(max_new_tokens=args.max_new_tokens, use_sam2_video_branch=video, **SAMPLING[mode])
-    recs = {dg: dict(llm=llm, mode=mode, decode_gemv=dg, branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
+    recs = {dg: dict(llm=llm, mode=mode, decode_gemv=dg[0], decode_weights=dg[1], branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
                      clips_ms={}, loop_ms={}, clips_spread={}, loop_spread={}, clips_ms_per_clip={}, loop_ms_per_clip={}, rows_step_ms={},
                      rows_step_spread={}) for dg in models}
     spread = lambda v: [round(min(v), 4), round(max(v), 4)]              # noqa: E731
@@ -114,13 +127,19 @@ def main():
     ap.add_argument("--branch", default="framewise", choices=["framewise", "video"])
     ap.add_argument("--sample", nargs="*", default=None, choices=["k50", "k0"], help="also (or, given alone with --no-greedy, only) the sampled modes")
     ap.add_argument("--no-greedy", action="store_true")
-    ap.add_argument("--decode-gemv", nargs="+", default=["valu"], choices=["valu", "mfma"],
-                    help="cfg['llm']['decode_gemv']; both: the modes alternate inside each repetition, one line per mode")
+    ap.add_argument("--decode-gemv", nargs="+", default=["valu"], choices=["valu", "mfma", "mfma_q"],
+                    help="cfg['llm']['decode_gemv']; several: the modes alternate inside each repetition, one line per mode")
+    ap.add_argument("--decode-weights", nargs="+", default=["bf16"], choices=["bf16", "fp8", "mxfp4"],
+                    help="cfg['llm']['decode_weights']; every valid pair with --decode-gemv is one model, invalid pairs are skipped")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     device = torch.device("cuda", 0)
     modes = ([] if args.no_greedy else ["greedy"]) + list(args.sample or [])
+    for dw in args.decode_weights:
+        for dg in args.decode_gemv:
+            if (dg, dw) not in pairs(args):
+                print(f"# skipped: decode_gemv = {dg} does not combine with decode_weights = {dw}", flush=True)
     for llm in args.llm:
         for mode in modes:
             for rec in run(llm, mode, args, device):

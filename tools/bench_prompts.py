@@ -12,12 +12,12 @@ differ in their 30 question ids.  One JSON line per LLM:
 --ab also times inference_prompts() with VG_PROMPTS_BATCHED=0 ("prompts_seq_ms"[B]: the prompts decoded one after another).
 --shared passes shared=True: the shared route for every model.  An mxfp4 model takes it only then (its default is one inference() per prompt, which
 is what "sequential_ms" times), so --decode-weights mxfp4 --shared --ab compares the batched MXFP4 step with the sequential loop on that route.
---decode-gemv mfma: the decode mode cfg["llm"]["decode_gemv"] = "mfma" (bf16 decode weights only), written into each line; given both values, one
+--decode-gemv mfma / mfma_q: the decode modes cfg["llm"]["decode_gemv"] = "mfma" (bf16 decode weights only) / "mfma_q" (fp8 / mxfp4 only), written into each line; given both values, one
 line per mode, each LLM's two runs back to back.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 11's table lives in profiles/).
 
     python tools/bench_prompts.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8] [--steps 3] [--warmup 1] [--branch framewise]
-                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--shared] [--ab] [--decode-gemv valu mfma]
+                                   [--decode-weights fp8|mxfp4] [--prefill fp8] [--shared] [--ab] [--decode-gemv valu mfma mfma_q]
                                    [--out FILE]
 """
 import argparse
@@ -145,13 +145,18 @@ def main():
     ap.add_argument("--prefill", default="bf16", choices=["bf16", "fp8"], help="fp8: the LLM prefill GEMMs on the fp8 MFMA path, as bench.py --prefill")
     ap.add_argument("--shared", action="store_true", help="call inference_prompts(..., shared=True): the shared route for every model, mxfp4 included")
     ap.add_argument("--ab", action="store_true", help="also time inference_prompts() on the sequential loop (VG_PROMPTS_BATCHED=0)")
-    ap.add_argument("--decode-gemv", nargs="+", default=["valu"], choices=["valu", "mfma"], help="cfg['llm']['decode_gemv']; one line per value")
+    ap.add_argument("--decode-gemv", nargs="+", default=["valu"], choices=["valu", "mfma", "mfma_q"],
+                    help="cfg['llm']['decode_gemv']; one line per value (mfma: bf16 decode weights only; mfma_q: fp8 / mxfp4 only; an invalid pair "
+                         "with --decode-weights is skipped with a printed line)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     device = torch.device("cuda", 0)
     for llm in args.llm:
         for dg in args.decode_gemv:
+            if (dg == "mfma" and args.decode_weights != "bf16") or (dg == "mfma_q" and args.decode_weights == "bf16"):
+                print(f"# skipped: decode_gemv = {dg} does not combine with decode_weights = {args.decode_weights}", flush=True)
+                continue
             line = json.dumps(run(llm, args, device, dg))
             print(line, flush=True)
             if args.out:

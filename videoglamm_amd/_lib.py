@@ -58,6 +58,10 @@ def _sig(lib):
         "vg_decode_gemv_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_gemm_rows_supported": ([I, I], c_int),
         "vg_decode_gemm_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
+        "vg_decode_gemm_w8_rows_supported": ([I, I], c_int),
+        "vg_decode_gemm_w8_rows": ([P, L, P, L, P, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
+        "vg_decode_gemm_w4_rows_supported": ([I, I], c_int),
+        "vg_decode_gemm_w4_rows": ([P, L, P, L, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_gemv_w8_rows_supported": ([I], c_int),
         "vg_decode_gemv_w8_rows": ([P, L, P, L, P, P, L, P, F, P, L, I, I, I, I, I, P], c_int),
         "vg_decode_gemv_w4_rows_supported": ([I], c_int),

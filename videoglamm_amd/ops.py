@@ -949,6 +949,57 @@ def decode_gemm_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_d
     return y
 
 
+def decode_gemm_w8_rows_supported(N, K):
+    """True when the MFMA B-row projection on fp8 weights covers a [N, K] weight (vg_decode_gemm_w8_rows_supported)."""
+    return bool(_lib.load().vg_decode_gemm_w8_rows_supported(int(N), int(K)))
+
+
+def decode_gemm_w8_rows(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """decode_gemm_rows on fp8 (e4m3) weights + per-row scales (vg_decode_gemm_w8_rows; the mode decode_gemv = "mfma_q"): x bf16 [B,K], B <= 16;
+    w8 uint8 [N or 2N, K] -> [B,N] of out_dtype (bf16 | fp32).  Row b equals the one-row call on row b bit for bit."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w8.dtype == torch.uint8 and w8.stride(1) == 1 and w8.shape[1] == K
+    assert wscale.dtype == torch.float32 and wscale.numel() == w8.shape[0] and wscale.is_contiguous()
+    N = w8.shape[0] // 2 if glu else w8.shape[0]
+    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
+    assert y.shape == (B, N) and y.stride(1) == 1
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
+        ldr = residual.stride(0)
+    rc = lib.vg_decode_gemm_w8_rows(_p(x), x.stride(0), _p(w8), w8.stride(0), _p(wscale), _p(y), y.stride(0),
+                                    _p(None if norm_w is None else _f32(norm_w)), float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y),
+                                    _stream())
+    _lib.check(rc, "vg_decode_gemm_w8_rows")
+    return y
+
+
+def decode_gemm_w4_rows_supported(N, K):
+    """True when the MFMA B-row projection on packed MXFP4 rows covers a [N, K] weight (vg_decode_gemm_w4_rows_supported)."""
+    return bool(_lib.load().vg_decode_gemm_w4_rows_supported(int(N), int(K)))
+
+
+def decode_gemm_w4_rows(x, w4, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """decode_gemm_rows on the packed MXFP4 rows of mxfp4_pack (vg_decode_gemm_w4_rows; the mode decode_gemv = "mfma_q"): x bf16 [B,K], B <= 16
+    -> [B,N] of out_dtype (bf16 | fp32).  Row b equals the one-row call on row b bit for bit; a block with scale byte 0 counts as zero."""
+    lib = _lib.load()
+    B, K = x.shape
+    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w4.dtype == torch.uint8 and w4.stride(1) == 1
+    assert K not in MXFP4_K or w4.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
+    N = w4.shape[0] // 2 if glu else w4.shape[0]
+    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
+    assert y.shape == (B, N) and y.stride(1) == 1
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
+        ldr = residual.stride(0)
+    rc = lib.vg_decode_gemm_w4_rows(_p(x), x.stride(0), _p(w4), w4.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)),
+                                    float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y), _stream())
+    _lib.check(rc, "vg_decode_gemm_w4_rows")
+    return y
+
+
 def decode_gemv_w8_rows_supported(K):
     """True when the B-row fp8 GEMV has the row length K (vg_decode_gemv_w8_rows_supported: 3072, 4096, 8192, 14336)."""
     return bool(_lib.load().vg_decode_gemv_w8_rows_supported(int(K)))

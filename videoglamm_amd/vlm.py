@@ -163,29 +163,45 @@ class VisionTowers:
         return torch.cat([cf, vf], dim=0)
 
 
-def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, supported):
+def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, supported, quant_projections=(), quant_supported=None):
     """cfg["llm"]["decode_gemv"]: False for None / "valu" (the decode GEMVs of DESIGN 5d / 11), True for "mfma" (every plain projection of the
-    single-row and the B-row step on vg_decode_gemm_rows) — or a ValueError that names why this decoder cannot take the mode.
+    single-row and the B-row step on vg_decode_gemm_rows), "mfma_q" for "mfma_q" (the same step with fp8 / mxfp4 decode weights: the
+    quantised projections on vg_decode_gemm_w8_rows / vg_decode_gemm_w4_rows, the bf16 ones on vg_decode_gemm_rows) — or a ValueError that names
+    why this decoder cannot take the mode.
     decode_weights: cfg["llm"]["decode_weights"]; dtype: the model's; env: the environment; step: "rope" (Llama-3 width: q|k|v + RoPE + append
     stays on its own kernel), "attention" (Phi-3-mini width: the q|k|v GEMV moves too) or None (neither B-row step covers the decoder);
-    projections: the (N, K) of the weights the mode moves; supported: ops.decode_gemm_rows_supported.  Pure: no device work."""
+    projections: the (N, K) of the bf16 weights the mode moves; supported: ops.decode_gemm_rows_supported.  "mfma_q" only: quant_projections: the
+    (N, K, kind, norm) of the quantised weights — kind "w8" | "w4", norm: the projection runs behind a fused RMSNorm — and quant_supported:
+    {"w8": ops.decode_gemm_w8_rows_supported, "w4": ops.decode_gemm_w4_rows_supported}.  Pure: no device work."""
     if value in (None, "valu"):
         return False
-    if value != "mfma":
-        raise ValueError(f"cfg['llm']['decode_gemv'] = {value!r}: 'valu' (default) or 'mfma'")
-    if decode_weights in ("fp8", "mxfp4"):
-        raise ValueError(f"decode_gemv = 'mfma' streams the bf16 weights: it does not combine with decode_weights = {decode_weights!r}")
+    if value not in ("mfma", "mfma_q"):
+        raise ValueError(f"cfg['llm']['decode_gemv'] = {value!r}: 'valu' (default), 'mfma' or 'mfma_q'")
+    if value == "mfma" and decode_weights in ("fp8", "mxfp4"):
+        raise ValueError(f"decode_gemv = 'mfma' streams the bf16 weights: it does not combine with decode_weights = {decode_weights!r} "
+                         "(decode_gemv = 'mfma_q' does)")
+    if value == "mfma_q" and decode_weights not in ("fp8", "mxfp4"):
+        raise ValueError(f"decode_gemv = 'mfma_q' streams fp8 / mxfp4 decode weights, not decode_weights = {decode_weights!r}: with bf16 weights "
+                         "the mode is decode_gemv = 'mfma'")
     if dtype != torch.bfloat16:
-        raise ValueError(f"decode_gemv = 'mfma' needs a bf16 model (v_mfma_f32_16x16x32_bf16), not {dtype}")
+        raise ValueError(f"decode_gemv = {value!r} needs a bf16 model (v_mfma_f32_16x16x32_bf16), not {dtype}")
     for knob in ("VG_DECODE_CHAIN", "VG_DECODE_AHEAD"):
         if env.get(knob, "0") != "0":
-            raise ValueError(f"decode_gemv = 'mfma' does not combine with {knob}={env.get(knob)}")
+            raise ValueError(f"decode_gemv = {value!r} does not combine with {knob}={env.get(knob)}")
     if step not in ("rope", "attention"):
-        raise ValueError("decode_gemv = 'mfma': this decoder takes neither the rope step (Llama-3 width) nor the decode_attention rows step (Phi-3-mini width)")
+        raise ValueError(f"decode_gemv = {value!r}: this decoder takes neither the rope step (Llama-3 width) nor the decode_attention rows step (Phi-3-mini width)")
     for N, K in projections:
         if not supported(N, K):
-            raise ValueError(f"decode_gemv = 'mfma': vg_decode_gemm_rows does not cover a [{N}, {K}] projection (uncovered width)")
-    return True
+            raise ValueError(f"decode_gemv = {value!r}: vg_decode_gemm_rows does not cover a [{N}, {K}] projection (uncovered width)")
+    if value == "mfma":
+        return True
+    for N, K, kind, norm in quant_projections:
+        if not quant_supported[kind](N, K):
+            raise ValueError(f"decode_gemv = 'mfma_q': vg_decode_gemm_{kind}_rows does not cover a [{N}, {K}] projection (uncovered width)")
+        if norm and K > 4096:
+            raise ValueError(f"decode_gemv = 'mfma_q': the RMSNorm-fused form of vg_decode_gemm_{kind}_rows exists at K <= 4096 only, "
+                             f"not for the [{N}, {K}] projection behind the norm (hidden {K})")
+    return "mfma_q"
 
 
 class LlamaDecoder:
@@ -264,6 +280,7 @@ class LlamaDecoder:
         self.rope_path = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
                           and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
         self.kpw2 = int(os.environ.get("VG_DEC2_KPW", "256"))
+        # cfg["decode_gemv"] == "mfma_q": the same with fp8 / mxfp4 decode weights, on the MFMA kernels that convert the weight bytes on the way.
         # cfg["decode_gemv"] == "mfma": the plain projections of the decode step (o, gate|up, down, the lm_head; q|k|v too on the decode_attention
         # step) run on vg_decode_gemm_rows, single-row step and B-row step alike; absent / "valu": the decode GEMVs above
         step = None
@@ -271,12 +288,21 @@ class LlamaDecoder:
             step = "rope"
         elif self.fused_decode and dev.type == "cuda" and not self.chain_roles and ops.decode_step_rows_supported(self.H, self.Hkv, self.hd, self.D, ffn, dt):
             step = "attention"
-        proj = []
+        proj, qproj = [], []
         if c.get("decode_gemv") == "mfma":
             proj = [(self.D, self.H * self.hd), (ffn, self.D), (self.D, ffn), (params.t("lm_head.weight").shape[0], self.D)]
             if step == "attention":
                 proj.append(((self.H + 2 * self.Hkv) * self.hd, self.D))
-        self.mfma = decode_gemv_mode(c.get("decode_gemv"), c.get("decode_weights"), dt, os.environ, step, proj, ops.decode_gemm_rows_supported)
+        elif c.get("decode_gemv") == "mfma_q":
+            # o (and q|k|v on the decode_attention step) stay bf16; gate|up (behind the norm) and down in the decode weights' format, the lm_head fp8
+            proj = [(self.D, self.H * self.hd)] + ([((self.H + 2 * self.Hkv) * self.hd, self.D)] if step == "attention" else [])
+            kind = "w4" if self.w4 else "w8"
+            qproj = [(ffn, self.D, kind, True), (self.D, ffn, kind, False), (params.t("lm_head.weight").shape[0], self.D, "w8", False)]
+        mode = decode_gemv_mode(c.get("decode_gemv"), c.get("decode_weights"), dt, os.environ, step, proj, ops.decode_gemm_rows_supported,
+                                quant_projections=qproj,
+                                quant_supported={"w8": ops.decode_gemm_w8_rows_supported, "w4": ops.decode_gemm_w4_rows_supported})
+        # mfma: decode_gemv = "mfma" (bf16 weights); mfma_q: decode_gemv = "mfma_q" (fp8 / mxfp4 weights)
+        self.mfma, self.mfma_q = mode is True, mode == "mfma_q"
         # sampled decoding (vg_sample): None = greedy; else dict(T, k, p, seed), the values held in the device block samp_params that
         # the captured step reads — a new temperature / top-p / top-k / seed is a copy into it, never a re-capture
         self.sampling, self.samp_params, self.samp_ws, self.samp_fast = None, None, None, False
@@ -355,7 +381,9 @@ class LlamaDecoder:
                 self.chain_err = torch.zeros((), dtype=torch.int32, device=x.device)
             self.chain_err.add_(self.chain_flags[:, 1].sum())      # the previous token's gave-up words survive the memset below (generate() checks)
             self.chain_flags.zero_()          # one memset per token: every layer's arrival stripes and go flags
-        gemv = ops.decode_gemm_rows if self.mfma else ops.decode_gemv      # the mode: the B-row kernel with B = 1, the batched step's twin
+        gemv = ops.decode_gemm_rows if self.mfma or self.mfma_q else ops.decode_gemv      # the modes: the B-row kernel with B = 1, the batched step's twin
+        gemv_w8 = ops.decode_gemm_w8_rows if self.mfma_q else ops.decode_gemv_w8
+        gemv_w4 = ops.decode_gemm_w4_rows if self.mfma_q else ops.decode_gemv_w4
         if self.rope_path and rope_row:
             ops.decode_advance_(self.pos_dev, 0, rope=(self.cos, self.sin, self.rope_cs))      # the cos / sin row of *pos_dev, once per token (decode_step_begin does it inside a captured step)
         for i in range(c["num_layers"]):
@@ -394,13 +422,13 @@ class LlamaDecoder:
             if self.w8:
                 # fp8 weights + row scales for the MLP (81 % of a layer's bytes) — the attention projections stay bf16: at K = 4096
                 # an fp8 row is a single batch of loads per lane and the per-row reduction eats the gain (10.4 vs 9.1 us measured)
-                a = ops.decode_gemv_w8(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                                       eps=c["rms_eps"], glu=True)
-                x = ops.decode_gemv_w8(a, *P.fp8(l + "mlp.down_proj"), residual=x)
+                a = gemv_w8(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                            eps=c["rms_eps"], glu=True)
+                x = gemv_w8(a, *P.fp8(l + "mlp.down_proj"), residual=x)
             elif self.w4:
-                a = ops.decode_gemv_w4(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                                       eps=c["rms_eps"], glu=True)
-                x = ops.decode_gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
+                a = gemv_w4(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                            eps=c["rms_eps"], glu=True)
+                x = gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
             else:
                 wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
                 a = gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
@@ -460,7 +488,8 @@ class LlamaDecoder:
     def next_token(self, hidden_row):
         """lm_head + argmax (or, sampling, the warpers + the draw of step *step_dev) of one final-norm row -> tok_dev (device int64[1])."""
         if (self.w8 or self.w4) and hidden_row.shape[0] == 1:
-            logits = ops.decode_gemv_w8(hidden_row.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
+            gemv_w8 = ops.decode_gemm_w8_rows if self.mfma_q else ops.decode_gemv_w8
+            logits = gemv_w8(hidden_row.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
         elif self.mfma and hidden_row.shape[0] == 1:
             logits = ops.decode_gemm_rows(hidden_row.contiguous(), self.P.w("lm_head"), out_dtype=torch.float32)
         else:
@@ -484,7 +513,8 @@ class LlamaDecoder:
                                   rope=(self.cos, self.sin, self.rope_cs) if self.rope_path else None)
         h = self._layers_decode(x, rope_row=False)
         if self.w8 or self.w4:
-            logits = ops.decode_gemv_w8(h.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
+            gemv_w8 = ops.decode_gemm_w8_rows if self.mfma_q else ops.decode_gemv_w8
+            logits = gemv_w8(h.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
         elif self.mfma:
             logits = ops.decode_gemm_rows(h.contiguous(), self.P.w("lm_head"), out_dtype=torch.float32)
         else:
@@ -552,7 +582,9 @@ class RowsDecode:
     rows pick 64 or 128 keys per workgroup on the device from their own position and dec.kpw_min; kw = ATTN_KW).
     The projections follow the decoder's decode weights: bf16 (vg_decode_gemv_rows; with cfg["decode_gemv"] = "mfma" vg_decode_gemm_rows, the
     lm_head included, which is also what the decoder's single-row step then runs), fp8 (the MLP and the lm_head on vg_decode_gemv_w8_rows) or
-    mxfp4 (the MLP on vg_decode_gemv_w4_rows, the lm_head on vg_decode_gemv_w8_rows); the attention projections are bf16 in all three.
+    mxfp4 (the MLP on vg_decode_gemv_w4_rows, the lm_head on vg_decode_gemv_w8_rows); the attention projections are bf16 in all three.  With
+    cfg["decode_gemv"] = "mfma_q" the fp8 / mxfp4 projections run on vg_decode_gemm_w8_rows / vg_decode_gemm_w4_rows and the bf16 o (and Phi-3's
+    q|k|v) on vg_decode_gemm_rows — again the kernels of the decoder's single-row step.
     The step is captured once per sampling route ("greedy" / "sample_fast" / "sample") into a HIP graph; a new seed or temperature is a copy into
     samp_params.  Rows past the live prompts (bucket padding) and retired rows keep computing into their own slots; their tokens are ignored."""
 
@@ -616,7 +648,9 @@ class RowsDecode:
 
     def _step(self):
         d, P, c = self.dec, self.dec.P, self.dec.c
-        gemv = ops.decode_gemm_rows if d.mfma else ops.decode_gemv_rows      # decode_gemv = "mfma": the kernel of the decoder's single-row step
+        gemv = ops.decode_gemm_rows if d.mfma or d.mfma_q else ops.decode_gemv_rows      # decode_gemv = "mfma" / "mfma_q": the kernels of the decoder's single-row step
+        gemv_w8 = ops.decode_gemm_w8_rows if d.mfma_q else ops.decode_gemv_w8_rows
+        gemv_w4 = ops.decode_gemm_w4_rows if d.mfma_q else ops.decode_gemv_w4_rows
         x = ops.decode_step_begin_rows(self.tok, P.t("model.embed_tokens.weight"), self.pos,
                                        rope=None if self.attn_rows else (d.cos, d.sin, self.rope_cs))
         for i in range(c["num_layers"]):
@@ -636,22 +670,22 @@ class RowsDecode:
             if d.w8:
                 # fp8 decode weights: the MLP and (below) the lm_head on the B-row fp8 GEMV, the operands LlamaDecoder._layers_decode picks; the
                 # attention projections stay bf16 as they do there
-                a = ops.decode_gemv_w8_rows(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                                            eps=c["rms_eps"], glu=True)
-                x = ops.decode_gemv_w8_rows(a, *P.fp8(l + "mlp.down_proj"), residual=x)
+                a = gemv_w8(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                            eps=c["rms_eps"], glu=True)
+                x = gemv_w8(a, *P.fp8(l + "mlp.down_proj"), residual=x)
             elif d.w4:
                 # MXFP4 decode weights: the MLP on the B-row MXFP4 GEMV (packed rows, Params.fp4), the lm_head (below) on the fp8 one — the
                 # operands of the single-row step
-                a = ops.decode_gemv_w4_rows(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                                            eps=c["rms_eps"], glu=True)
-                x = ops.decode_gemv_w4_rows(a, P.fp4(l + "mlp.down_proj"), residual=x)
+                a = gemv_w4(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
+                            eps=c["rms_eps"], glu=True)
+                x = gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
             else:
                 wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
                 a = gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
                 x = gemv(a, P.w(l + "mlp.down_proj"), residual=x)
         h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
         if d.w8 or d.w4:
-            logits = ops.decode_gemv_w8_rows(h, *P.fp8("lm_head"), out_dtype=torch.float32)
+            logits = gemv_w8(h, *P.fp8("lm_head"), out_dtype=torch.float32)
         elif d.mfma:
             logits = ops.decode_gemm_rows(h, P.w("lm_head"), out_dtype=torch.float32)
         else:

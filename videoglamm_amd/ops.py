@@ -568,22 +568,27 @@ def rope_kv_append_(qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos0=0, pos_dev=
     return qkv
 
 
-def decode_gemv(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
-    """Decode-step projection of ONE row: y[N] = rmsnorm(x; norm_w, eps) (or x) @ w^T, optional SwiGLU over w = [gate|up]
-    rows and optional residual — HF LlamaRMSNorm + nn.Linear (+ LlamaMLP act) in one launch (vg_decode_gemv)."""
-    lib = _lib.load()
+def _decode_proj(entry, x, w, mid, norm_w, eps, residual, glu, out_dtype, out, x_code=False):
+    """the shared body of the single-row decode projections (decode_gemv / _w8 / _w4): y [1,N] chosen or allocated and checked with the residual,
+    then entry(x, w, ldw, *mid, y, norm_w, eps, residual, N, K, glu, [dtype code of x,] dtype code of y, stream)"""
     K = x.shape[-1]
-    assert x.numel() == K and x.is_contiguous() and w.stride(1) == 1 and w.shape[1] == K
     N = w.shape[0] // 2 if glu else w.shape[0]
-    odt = out_dtype or x.dtype
-    y = out if out is not None else torch.empty(1, N, dtype=odt, device=x.device)
+    y = out if out is not None else torch.empty(1, N, dtype=out_dtype or x.dtype, device=x.device)
     assert y.is_contiguous() and y.numel() == N
     if residual is not None:
         assert residual.is_contiguous() and residual.numel() == N and residual.dtype == y.dtype
-    rc = lib.vg_decode_gemv(_p(x), _p(w), w.stride(0), _p(y), _p(None if norm_w is None else _f32(norm_w)), float(eps),
-                            _p(residual), N, K, int(bool(glu)), _dt(x), _dt(y), _stream())
-    _lib.check(rc, "vg_decode_gemv")
+    rc = getattr(_lib.load(), entry)(_p(x), _p(w), w.stride(0), *mid, _p(y), _p(None if norm_w is None else _f32(norm_w)), float(eps),
+                                     _p(residual), N, K, int(bool(glu)), *((_dt(x),) if x_code else ()), _dt(y), _stream())
+    _lib.check(rc, entry)
     return y
+
+
+def decode_gemv(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """Decode-step projection of ONE row: y[N] = rmsnorm(x; norm_w, eps) (or x) @ w^T, optional SwiGLU over w = [gate|up]
+    rows and optional residual — HF LlamaRMSNorm + nn.Linear (+ LlamaMLP act) in one launch (vg_decode_gemv)."""
+    K = x.shape[-1]
+    assert x.numel() == K and x.is_contiguous() and w.stride(1) == 1 and w.shape[1] == K
+    return _decode_proj("vg_decode_gemv", x, w, (), norm_w, eps, residual, glu, out_dtype, out, x_code=True)
 
 
 def quantize_fp8_rows(w):
@@ -625,20 +630,10 @@ def linear_f8(q, qs, w8, ws, bias=None, residual=None, glu=False, out_dtype=torc
 
 def decode_gemv_w8(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """decode_gemv with fp8 (e4m3) weights + per-row scales (vg_decode_gemv_w8): x bf16 [1,K]; w8 uint8 [N or 2N, K]."""
-    lib = _lib.load()
     K = x.shape[-1]
     assert x.dtype == torch.bfloat16 and x.numel() == K and x.is_contiguous() and w8.dtype == torch.uint8 and w8.stride(1) == 1 and w8.shape[1] == K
     assert wscale.dtype == torch.float32 and wscale.numel() == w8.shape[0] and wscale.is_contiguous()
-    N = w8.shape[0] // 2 if glu else w8.shape[0]
-    odt = out_dtype or x.dtype
-    y = out if out is not None else torch.empty(1, N, dtype=odt, device=x.device)
-    assert y.is_contiguous() and y.numel() == N
-    if residual is not None:
-        assert residual.is_contiguous() and residual.numel() == N and residual.dtype == y.dtype
-    rc = lib.vg_decode_gemv_w8(_p(x), _p(w8), w8.stride(0), _p(wscale), _p(y), _p(None if norm_w is None else _f32(norm_w)), float(eps),
-                               _p(residual), N, K, int(bool(glu)), _dt(y), _stream())
-    _lib.check(rc, "vg_decode_gemv_w8")
-    return y
+    return _decode_proj("vg_decode_gemv_w8", x, w8, (_p(wscale),), norm_w, eps, residual, glu, out_dtype, out)
 
 
 MXFP4_K = {3072: 2, 4096: 2, 8192: 4, 14336: 8}      # row lengths of vg_decode_gemv_w4 -> SPL, scale bytes per lane in a packed row's head
@@ -697,23 +692,13 @@ def mxfp4_dequant(codes, scales=None, K=None):
 def decode_gemv_w4(x, w4, scales=None, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """decode_gemv with MXFP4 weights (vg_decode_gemv_w4): x bf16 [1,K]; w4 uint8, N or 2N rows: packed rows (mxfp4_pack; scales None) or the
     logical codes [rows, K/2] with scales uint8 [rows, K/32]."""
-    lib = _lib.load()
     K = x.shape[-1]
     assert x.dtype == torch.bfloat16 and x.numel() == K and x.is_contiguous() and w4.dtype == torch.uint8 and w4.stride(1) == 1
     if scales is not None:
         assert scales.dtype == torch.uint8 and scales.shape == (w4.shape[0], K // 32) and scales.is_contiguous() and w4.shape[1] == K // 2
     else:
         assert K not in MXFP4_K or w4.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
-    N = w4.shape[0] // 2 if glu else w4.shape[0]
-    odt = out_dtype or x.dtype
-    y = out if out is not None else torch.empty(1, N, dtype=odt, device=x.device)
-    assert y.is_contiguous() and y.numel() == N
-    if residual is not None:
-        assert residual.is_contiguous() and residual.numel() == N and residual.dtype == y.dtype
-    rc = lib.vg_decode_gemv_w4(_p(x), _p(w4), w4.stride(0), _p(scales), _p(y), _p(None if norm_w is None else _f32(norm_w)), float(eps),
-                               _p(residual), N, K, int(bool(glu)), _dt(y), _stream())
-    _lib.check(rc, "vg_decode_gemv_w4")
-    return y
+    return _decode_proj("vg_decode_gemv_w4", x, w4, (_p(scales),), norm_w, eps, residual, glu, out_dtype, out)
 
 
 def decode_attention_workspace(H, Hkv, D, max_len, device):
@@ -906,22 +891,29 @@ def decode_rows_supported(H, Hkv, D, hidden, inter, dtype):
     return dtype == torch.bfloat16 and bool(_lib.load().vg_decode_rows_supported(H, Hkv, D, hidden, inter, BF16))
 
 
-def decode_gemv_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out=None):
-    """decode_gemv on each of the B rows of x [B,K] (vg_decode_gemv_rows): one pass over w for all rows -> [B,N]."""
-    lib = _lib.load()
+def _decode_proj_rows(entry, x, w, mid, norm_w, eps, residual, glu, out_dtype, out, x_code=False):
+    """the shared body of the B-row decode projections (decode_gemv_*rows / decode_gemm_*rows): x bf16 [B,K] with unit-stride rows, y [B,N] chosen
+    or allocated and checked with the residual, then entry(x, ldx, w, ldw, *mid, y, ldy, norm_w, eps, residual, ldr, N, K, B, glu, dtype code of
+    y (x_code: of x), stream)"""
     B, K = x.shape
-    assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and x.dtype == torch.bfloat16
+    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w.stride(1) == 1
     N = w.shape[0] // 2 if glu else w.shape[0]
-    y = out if out is not None else torch.empty(B, N, dtype=x.dtype, device=x.device)
+    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
     assert y.shape == (B, N) and y.stride(1) == 1
     ldr = 0
     if residual is not None:
         assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
         ldr = residual.stride(0)
-    rc = lib.vg_decode_gemv_rows(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)), float(eps),
-                                 _p(residual), ldr, N, K, B, int(bool(glu)), _dt(x), _stream())
-    _lib.check(rc, "vg_decode_gemv_rows")
+    rc = getattr(_lib.load(), entry)(_p(x), x.stride(0), _p(w), w.stride(0), *mid, _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)),
+                                     float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(x if x_code else y), _stream())
+    _lib.check(rc, entry)
     return y
+
+
+def decode_gemv_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out=None):
+    """decode_gemv on each of the B rows of x [B,K] (vg_decode_gemv_rows): one pass over w for all rows -> [B,N]."""
+    assert w.shape[1] == x.shape[1]
+    return _decode_proj_rows("vg_decode_gemv_rows", x, w, (), norm_w, eps, residual, glu, None, out, x_code=True)
 
 
 def decode_gemm_rows_supported(N, K):
@@ -932,21 +924,8 @@ def decode_gemm_rows_supported(N, K):
 def decode_gemm_rows(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """The decode projection of the B <= 16 rows of x [B,K] on the matrix pipe (vg_decode_gemm_rows; the mode decode_gemv = "mfma") -> [B,N] of
     out_dtype (bf16 | fp32).  Row b equals the one-row call on row b bit for bit."""
-    lib = _lib.load()
-    B, K = x.shape
-    assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-    N = w.shape[0] // 2 if glu else w.shape[0]
-    od = out.dtype if out is not None else (out_dtype or x.dtype)
-    y = out if out is not None else torch.empty(B, N, dtype=od, device=x.device)
-    assert y.shape == (B, N) and y.stride(1) == 1 and y.dtype == od
-    ldr = 0
-    if residual is not None:
-        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
-        ldr = residual.stride(0)
-    rc = lib.vg_decode_gemm_rows(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)), float(eps),
-                                 _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y), _stream())
-    _lib.check(rc, "vg_decode_gemm_rows")
-    return y
+    assert w.shape[1] == x.shape[1] and w.dtype == torch.bfloat16
+    return _decode_proj_rows("vg_decode_gemm_rows", x, w, (), norm_w, eps, residual, glu, out_dtype, out)
 
 
 def decode_gemm_w8_rows_supported(N, K):
@@ -957,22 +936,9 @@ def decode_gemm_w8_rows_supported(N, K):
 def decode_gemm_w8_rows(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """decode_gemm_rows on fp8 (e4m3) weights + per-row scales (vg_decode_gemm_w8_rows; the mode decode_gemv = "mfma_q"): x bf16 [B,K], B <= 16;
     w8 uint8 [N or 2N, K] -> [B,N] of out_dtype (bf16 | fp32).  Row b equals the one-row call on row b bit for bit."""
-    lib = _lib.load()
-    B, K = x.shape
-    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w8.dtype == torch.uint8 and w8.stride(1) == 1 and w8.shape[1] == K
+    assert w8.dtype == torch.uint8 and w8.shape[1] == x.shape[1]
     assert wscale.dtype == torch.float32 and wscale.numel() == w8.shape[0] and wscale.is_contiguous()
-    N = w8.shape[0] // 2 if glu else w8.shape[0]
-    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
-    assert y.shape == (B, N) and y.stride(1) == 1
-    ldr = 0
-    if residual is not None:
-        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
-        ldr = residual.stride(0)
-    rc = lib.vg_decode_gemm_w8_rows(_p(x), x.stride(0), _p(w8), w8.stride(0), _p(wscale), _p(y), y.stride(0),
-                                    _p(None if norm_w is None else _f32(norm_w)), float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y),
-                                    _stream())
-    _lib.check(rc, "vg_decode_gemm_w8_rows")
-    return y
+    return _decode_proj_rows("vg_decode_gemm_w8_rows", x, w8, (_p(wscale),), norm_w, eps, residual, glu, out_dtype, out)
 
 
 def decode_gemm_w4_rows_supported(N, K):
@@ -983,21 +949,10 @@ def decode_gemm_w4_rows_supported(N, K):
 def decode_gemm_w4_rows(x, w4, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """decode_gemm_rows on the packed MXFP4 rows of mxfp4_pack (vg_decode_gemm_w4_rows; the mode decode_gemv = "mfma_q"): x bf16 [B,K], B <= 16
     -> [B,N] of out_dtype (bf16 | fp32).  Row b equals the one-row call on row b bit for bit; a block with scale byte 0 counts as zero."""
-    lib = _lib.load()
-    B, K = x.shape
-    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w4.dtype == torch.uint8 and w4.stride(1) == 1
+    K = x.shape[1]
+    assert w4.dtype == torch.uint8
     assert K not in MXFP4_K or w4.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
-    N = w4.shape[0] // 2 if glu else w4.shape[0]
-    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
-    assert y.shape == (B, N) and y.stride(1) == 1
-    ldr = 0
-    if residual is not None:
-        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
-        ldr = residual.stride(0)
-    rc = lib.vg_decode_gemm_w4_rows(_p(x), x.stride(0), _p(w4), w4.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)),
-                                    float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y), _stream())
-    _lib.check(rc, "vg_decode_gemm_w4_rows")
-    return y
+    return _decode_proj_rows("vg_decode_gemm_w4_rows", x, w4, (), norm_w, eps, residual, glu, out_dtype, out)
 
 
 def decode_gemv_w8_rows_supported(K):
@@ -1007,22 +962,9 @@ def decode_gemv_w8_rows_supported(K):
 
 def decode_gemv_w8_rows(x, w8, wscale, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """decode_gemv_w8 on each of the B rows of x [B,K] (vg_decode_gemv_w8_rows): one pass over the fp8 weights for all rows -> [B,N]."""
-    lib = _lib.load()
-    B, K = x.shape
-    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w8.dtype == torch.uint8 and w8.stride(1) == 1 and w8.shape[1] == K
+    assert w8.dtype == torch.uint8 and w8.shape[1] == x.shape[1]
     assert wscale.dtype == torch.float32 and wscale.numel() == w8.shape[0] and wscale.is_contiguous()
-    N = w8.shape[0] // 2 if glu else w8.shape[0]
-    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
-    assert y.shape == (B, N) and y.stride(1) == 1
-    ldr = 0
-    if residual is not None:
-        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
-        ldr = residual.stride(0)
-    rc = lib.vg_decode_gemv_w8_rows(_p(x), x.stride(0), _p(w8), w8.stride(0), _p(wscale), _p(y), y.stride(0),
-                                    _p(None if norm_w is None else _f32(norm_w)), float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y),
-                                    _stream())
-    _lib.check(rc, "vg_decode_gemv_w8_rows")
-    return y
+    return _decode_proj_rows("vg_decode_gemv_w8_rows", x, w8, (_p(wscale),), norm_w, eps, residual, glu, out_dtype, out)
 
 
 def decode_gemv_w4_rows_supported(K):
@@ -1033,21 +975,10 @@ def decode_gemv_w4_rows_supported(K):
 def decode_gemv_w4_rows(x, w4, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
     """decode_gemv_w4 on each of the B rows of x [B,K] (vg_decode_gemv_w4_rows): one pass over the packed MXFP4 rows (mxfp4_pack) for all rows
     -> [B,N]."""
-    lib = _lib.load()
-    B, K = x.shape
-    assert x.stride(1) == 1 and x.dtype == torch.bfloat16 and w4.dtype == torch.uint8 and w4.stride(1) == 1
+    K = x.shape[1]
+    assert w4.dtype == torch.uint8
     assert K not in MXFP4_K or w4.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
-    N = w4.shape[0] // 2 if glu else w4.shape[0]
-    y = out if out is not None else torch.empty(B, N, dtype=out_dtype or x.dtype, device=x.device)
-    assert y.shape == (B, N) and y.stride(1) == 1
-    ldr = 0
-    if residual is not None:
-        assert residual.shape == (B, N) and residual.stride(1) == 1 and residual.dtype == y.dtype
-        ldr = residual.stride(0)
-    rc = lib.vg_decode_gemv_w4_rows(_p(x), x.stride(0), _p(w4), w4.stride(0), _p(y), y.stride(0), _p(None if norm_w is None else _f32(norm_w)),
-                                    float(eps), _p(residual), ldr, N, K, B, int(bool(glu)), _dt(y), _stream())
-    _lib.check(rc, "vg_decode_gemv_w4_rows")
-    return y
+    return _decode_proj_rows("vg_decode_gemv_w4_rows", x, w4, (), norm_w, eps, residual, glu, out_dtype, out)
 
 
 def decode_qkv_rope_rows(x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out=None):

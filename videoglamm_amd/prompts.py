@@ -165,16 +165,9 @@ def rows_cover(params, dec):
     rope_rows = dec.rope_path and ops.decode_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype)
     attn_rows = (not dec.rope_path and dec.fused_decode and params.device.type == "cuda"
                  and ops.decode_step_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype))
-    # fp8 decode weights: gate|up and the lm_head run at K = hidden, down at K = ffn
-    w8_rows = dec.w8 and ops.decode_gemv_w8_rows_supported(dec.D) and ops.decode_gemv_w8_rows_supported(_ffn(params))
-    # mxfp4 decode weights: gate|up at K = hidden and down at K = ffn on the B-row MXFP4 GEMV, the lm_head (fp8) at K = hidden
-    w4_rows = (dec.w4 and ops.decode_gemv_w4_rows_supported(dec.D) and ops.decode_gemv_w4_rows_supported(_ffn(params))
-               and ops.decode_gemv_w8_rows_supported(dec.D))
-    if dec.mfma_q:      # decode_gemv = "mfma_q": the same projections on the MFMA kernels ([N, K]: gate|up per half, down, the lm_head)
-        D, ffn, vocab = dec.D, _ffn(params), params.t("lm_head.weight").shape[0]
-        w8_rows = dec.w8 and ops.decode_gemm_w8_rows_supported(ffn, D) and ops.decode_gemm_w8_rows_supported(D, ffn) and ops.decode_gemm_w8_rows_supported(vocab, D)
-        w4_rows = (dec.w4 and ops.decode_gemm_w4_rows_supported(ffn, D) and ops.decode_gemm_w4_rows_supported(D, ffn)
-                   and ops.decode_gemm_w8_rows_supported(vocab, D))
+    # fp8 / mxfp4 decode weights: every quantised weight of the step (dec.proj: gate|up, down, the lm_head) has a B-row kernel of its shape
+    quant = all(dec.proj.covered(N, K, fmt) for N, K, fmt, _ in dec.proj.weights(quantised=True))
+    w8_rows, w4_rows = dec.w8 and quant, dec.w4 and quant
     return rope_rows, dict(attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=w4_rows)
 
 

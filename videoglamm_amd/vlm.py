@@ -204,6 +204,80 @@ def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, suppo
     return "mfma_q"
 
 
+class DecodeProjections:
+    """Which ops entry point, which stored form of the weight and which [N, K] each projection of the LLM decode step takes — the one place where
+    the modes meet.  Roles: "qkv" (the decode_attention step only: the rope step keeps q|k|v inside decode_qkv_rope), "o",
+    "gate_up", "down", "lm_head".
+
+    Stored form (fmt): q|k|v and o are bf16 in every mode; gate|up and down follow cfg["decode_weights"] ("bf16" | "w8" = fp8 e4m3 + row scales |
+    "w4" = packed MXFP4 rows); the lm_head is fp8 under either quantised format (it decides the token ids and is 4 % of the bytes), else bf16.
+    Entry point: KERNELS[fmt], picked by cfg["decode_gemv"] and by whether the step is the single-row one (LlamaDecoder) or the B-row one
+    (RowsDecode, rows=True): under "mfma" / "mfma_q" both steps run the MFMA B-row kernels (B = 1 in the single-row step).  The bf16 lm_head of
+    the VALU modes is a plain ops.linear.  Entries are held as names and looked up in ops at call time.
+    gate_up runs behind the fused post_attention_layernorm with SwiGLU, qkv behind input_layernorm; o and down add the residual; the lm_head
+    gives fp32 logits."""
+    #          fmt      VALU single-row    VALU B-row             MFMA, either step
+    KERNELS = {"bf16": ("decode_gemv",    "decode_gemv_rows",    "decode_gemm_rows"),
+               "w8":   ("decode_gemv_w8", "decode_gemv_w8_rows", "decode_gemm_w8_rows"),
+               "w4":   ("decode_gemv_w4", "decode_gemv_w4_rows", "decode_gemm_w4_rows")}
+
+    def __init__(self, decode_gemv, decode_weights, hidden=0, ffn=0, vocab=0, qkv=0, attn=None, step=None):
+        """decode_gemv / decode_weights: the cfg values; hidden, ffn, vocab, qkv (rows of q|k|v), attn (heads x head_dim: o's K; default hidden):
+        the widths weights() reports; step: "rope" | "attention" | None as decode_gemv_mode's.  Pure: no device work."""
+        self.mfma = decode_gemv in ("mfma", "mfma_q")
+        mlp = {"fp8": "w8", "mxfp4": "w4"}.get(decode_weights, "bf16")
+        self.fmt = dict(qkv="bf16", o="bf16", gate_up=mlp, down=mlp, lm_head="bf16" if mlp == "bf16" else "w8")
+        attn = hidden if attn is None else attn
+        # role -> (N, K, behind a fused RMSNorm), in the order decode_gemv_mode is asked (gate|up: N per half)
+        self.shape = dict(o=(hidden, attn, False), gate_up=(ffn, hidden, True), down=(hidden, ffn, False), lm_head=(vocab, hidden, False))
+        if step == "attention":
+            self.shape["qkv"] = (qkv, hidden, True)
+
+    def entry(self, role, rows=False):
+        """the name of the ops function that runs `role` in the single-row (rows=False) or the B-row step"""
+        if role == "lm_head" and self.fmt[role] == "bf16" and not self.mfma:
+            return "linear"
+        return self.KERNELS[self.fmt[role]][2 if self.mfma else int(bool(rows))]
+
+    def weights(self, quantised=None):
+        """[(N, K, fmt, norm)] of the step's weights; quantised=False: the bf16 ones only, True: the fp8 / MXFP4 ones only"""
+        return [(N, K, self.fmt[r], norm) for r, (N, K, norm) in self.shape.items()
+                if quantised is None or quantised == (self.fmt[r] != "bf16")]
+
+    def covered(self, N, K, fmt, rows=True):
+        """True when the entry point of a [N, K] weight stored as fmt has that shape (the VALU GEMVs are asked by row length alone)"""
+        sup = getattr(ops, self.KERNELS[fmt][2 if self.mfma else int(bool(rows))] + "_supported")
+        return sup(N, K) if self.mfma else sup(K)
+
+    def operands(self, P, role, l=""):
+        """the weight operands of `role` in layer prefix l ("model.layers.3."), in the role's stored form: one tensor, or fp8's (codes, scales)"""
+        names, stored = {"qkv": ([l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"], l + "self_attn.qkv_proj"),
+                         "o": (l + "self_attn.o_proj", None), "gate_up": ([l + "mlp.gate_proj", l + "mlp.up_proj"], l + "mlp.gate_up_proj"),
+                         "down": (l + "mlp.down_proj", None), "lm_head": ("lm_head", None)}[role]
+        fmt = self.fmt[role]
+        if fmt == "w8":
+            return P.fp8(names, stored=stored)
+        if fmt == "w4":
+            return (P.fp4(names, stored=stored),)
+        return (P.w(names) if stored is None else P.fused(names, stored=stored)[0],)
+
+    def run(self, role, rows, P, l, x, **kw):
+        """launch `role` on x: kw = the entry point's norm_w / eps / glu / residual / out_dtype"""
+        return getattr(ops, self.entry(role, rows))(x, *self.operands(P, role, l), **kw)
+
+    def mlp(self, rows, P, l, x, eps):
+        """norm + gate|up + SwiGLU, then down + residual: the two MLP launches of a layer -> (the SwiGLU rows, the layer's output).  The caller
+        holds the SwiGLU rows until the next layer's: released here, the captured step lays its buffers out otherwise (measured: the B = 8 mfma_q
+        step 4.42 instead of 4.41 ms)"""
+        a = self.run("gate_up", rows, P, l, x, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=eps, glu=True)
+        return a, self.run("down", rows, P, l, a, residual=x)
+
+    def lm_head(self, rows, P, h):
+        """fp32 logits of the final-norm rows h (the single-row kernels take a contiguous row)"""
+        name = self.entry("lm_head", rows)
+        return getattr(ops, name)(h if rows or name == "linear" else h.contiguous(), *self.operands(P, "lm_head"), out_dtype=torch.float32)
+
+
 class LlamaDecoder:
     """HF LlamaModel / Phi3Model arithmetic (RMSNorm, rotate-half RoPE, GQA attention, SwiGLU) with a KV cache.  Phi-3 (the
     released checkpoint's LLM, R/model/videogpt_plus/model/language_model/phi3.py:29-40) is the same graph with the
@@ -280,26 +354,19 @@ class LlamaDecoder:
         self.rope_path = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
                           and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
         self.kpw2 = int(os.environ.get("VG_DEC2_KPW", "256"))
-        # cfg["decode_gemv"] == "mfma_q": the same with fp8 / mxfp4 decode weights, on the MFMA kernels that convert the weight bytes on the way.
-        # cfg["decode_gemv"] == "mfma": the plain projections of the decode step (o, gate|up, down, the lm_head; q|k|v too on the decode_attention
-        # step) run on vg_decode_gemm_rows, single-row step and B-row step alike; absent / "valu": the decode GEMVs above
+        # cfg["decode_gemv"] ("valu" | "mfma" | "mfma_q") x cfg["decode_weights"]: which kernel and stored weight each projection of the single-row
+        # and the B-row step takes is DecodeProjections' answer; decode_gemv_mode refuses what this decoder cannot run before any launch
         step = None
         if self.rope_path:
             step = "rope"
         elif self.fused_decode and dev.type == "cuda" and not self.chain_roles and ops.decode_step_rows_supported(self.H, self.Hkv, self.hd, self.D, ffn, dt):
             step = "attention"
-        proj, qproj = [], []
-        if c.get("decode_gemv") == "mfma":
-            proj = [(self.D, self.H * self.hd), (ffn, self.D), (self.D, ffn), (params.t("lm_head.weight").shape[0], self.D)]
-            if step == "attention":
-                proj.append(((self.H + 2 * self.Hkv) * self.hd, self.D))
-        elif c.get("decode_gemv") == "mfma_q":
-            # o (and q|k|v on the decode_attention step) stay bf16; gate|up (behind the norm) and down in the decode weights' format, the lm_head fp8
-            proj = [(self.D, self.H * self.hd)] + ([((self.H + 2 * self.Hkv) * self.hd, self.D)] if step == "attention" else [])
-            kind = "w4" if self.w4 else "w8"
-            qproj = [(ffn, self.D, kind, True), (self.D, ffn, kind, False), (params.t("lm_head.weight").shape[0], self.D, "w8", False)]
-        mode = decode_gemv_mode(c.get("decode_gemv"), c.get("decode_weights"), dt, os.environ, step, proj, ops.decode_gemm_rows_supported,
-                                quant_projections=qproj,
+        head = params.sd.get("lm_head.weight")       # (a decoder that only prefills may come without one)
+        self.proj = DecodeProjections(c.get("decode_gemv"), c.get("decode_weights"), hidden=self.D, ffn=ffn, vocab=0 if head is None else head.shape[0],
+                                      qkv=(self.H + 2 * self.Hkv) * self.hd, attn=self.H * self.hd, step=step)
+        mode = decode_gemv_mode(c.get("decode_gemv"), c.get("decode_weights"), dt, os.environ, step,
+                                [(N, K) for N, K, _, _ in self.proj.weights(quantised=False)], ops.decode_gemm_rows_supported,
+                                quant_projections=self.proj.weights(quantised=True),
                                 quant_supported={"w8": ops.decode_gemm_w8_rows_supported, "w4": ops.decode_gemm_w4_rows_supported})
         # mfma: decode_gemv = "mfma" (bf16 weights); mfma_q: decode_gemv = "mfma_q" (fp8 / mxfp4 weights)
         self.mfma, self.mfma_q = mode is True, mode == "mfma_q"
@@ -381,58 +448,39 @@ class LlamaDecoder:
                 self.chain_err = torch.zeros((), dtype=torch.int32, device=x.device)
             self.chain_err.add_(self.chain_flags[:, 1].sum())      # the previous token's gave-up words survive the memset below (generate() checks)
             self.chain_flags.zero_()          # one memset per token: every layer's arrival stripes and go flags
-        gemv = ops.decode_gemm_rows if self.mfma or self.mfma_q else ops.decode_gemv      # the modes: the B-row kernel with B = 1, the batched step's twin
-        gemv_w8 = ops.decode_gemm_w8_rows if self.mfma_q else ops.decode_gemv_w8
-        gemv_w4 = ops.decode_gemm_w4_rows if self.mfma_q else ops.decode_gemv_w4
+        pr = self.proj
         if self.rope_path and rope_row:
             ops.decode_advance_(self.pos_dev, 0, rope=(self.cos, self.sin, self.rope_cs))      # the cos / sin row of *pos_dev, once per token (decode_step_begin does it inside a captured step)
         for i in range(c["num_layers"]):
             l = f"model.layers.{i}."
-            qkv_names = [l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"]
-            gu_names = [l + "mlp.gate_proj", l + "mlp.up_proj"]
-            wqkv, _ = P.fused(qkv_names, stored=l + "self_attn.qkv_proj")
             if self.rope_path:
                 # norm -> q|k|v -> RoPE -> append in one launch; the attention starts on its K / V loads (4 launches per layer + the MLP's 2)
-                q = ops.decode_qkv_rope(x, wqkv, P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.kc[i], self.vc[i], self.rope_cs,
-                                        self.pos_dev, self.H, self.Hkv, self.hd)
+                q = ops.decode_qkv_rope(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.kc[i], self.vc[i],
+                                        self.rope_cs, self.pos_dev, self.H, self.Hkv, self.hd)
                 o = ops.decode_attention2(q, self.kc[i], self.vc[i], self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5, self.attn_ws,
                                           window=self.window, keys_per_wg=self.kpw2)
-                x = gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
-                qkv = None
+                x = pr.run("o", False, P, l, o, residual=x)
             else:
-                qkv = gemv(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
-            if qkv is None:
-                pass
-            elif self.chain_roles:
-                # r03: attention, o_proj and (bf16 Llama widths) the MLP as roles of ONE launch whose GEMV workgroups fetch their weight
-                # rows while the producer role still runs (vg_decode_layer) — bit-identical to the separate launches below
-                w_o = P.w(l + "self_attn.o_proj")
-                if self.chain_roles == 3 and not (self.w8 or self.w4):     # the chained MLP role streams bf16 weights only
-                    wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
+                qkv = pr.run("qkv", False, P, l, x, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
+                if self.chain_roles:
+                    # r03: attention, o_proj and (bf16 Llama widths) the MLP as roles of ONE launch whose GEMV workgroups fetch their weight
+                    # rows while the producer role still runs (vg_decode_layer) — bit-identical to the separate launches below
+                    w_o = P.w(l + "self_attn.o_proj")
+                    mlp = None
+                    if self.chain_roles == 3 and not (self.w8 or self.w4):     # the chained MLP role streams bf16 weights only
+                        wgu, _ = P.fused([l + "mlp.gate_proj", l + "mlp.up_proj"], stored=l + "mlp.gate_up_proj")
+                        mlp = (P.f32(l + "post_attention_layernorm.weight"), c["rms_eps"], wgu, P.w(l + "mlp.down_proj"))
                     x = ops.decode_layer(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5,
-                                         self.attn_ws, self.chain_flags[i], w_o, x, window=self.window,
-                                         mlp=(P.f32(l + "post_attention_layernorm.weight"), c["rms_eps"], wgu, P.w(l + "mlp.down_proj")))
-                    continue
-                x = ops.decode_layer(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5,
-                                     self.attn_ws, self.chain_flags[i], w_o, x, window=self.window)
-            else:
-                o = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd,
-                                         self.pos_dev, self.hd ** -0.5, self.attn_ws, window=self.window, keys_per_wg=self.kpw)
-                x = gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
-            if self.w8:
-                # fp8 weights + row scales for the MLP (81 % of a layer's bytes) — the attention projections stay bf16: at K = 4096
-                # an fp8 row is a single batch of loads per lane and the per-row reduction eats the gain (10.4 vs 9.1 us measured)
-                a = gemv_w8(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                            eps=c["rms_eps"], glu=True)
-                x = gemv_w8(a, *P.fp8(l + "mlp.down_proj"), residual=x)
-            elif self.w4:
-                a = gemv_w4(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                            eps=c["rms_eps"], glu=True)
-                x = gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
-            else:
-                wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
-                a = gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
-                x = gemv(a, P.w(l + "mlp.down_proj"), residual=x)
+                                         self.attn_ws, self.chain_flags[i], w_o, x, window=self.window, mlp=mlp)
+                    if mlp is not None:
+                        continue
+                else:
+                    o = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd,
+                                             self.pos_dev, self.hd ** -0.5, self.attn_ws, window=self.window, keys_per_wg=self.kpw)
+                    x = pr.run("o", False, P, l, o, residual=x)
+            # the MLP (81 % of a layer's bytes) in the decode weights' format — the attention projections stay bf16: at K = 4096 an fp8 row is
+            # a single batch of loads per lane and the per-row reduction eats the gain (10.4 vs 9.1 us measured)
+            a, x = pr.mlp(False, P, l, x, c["rms_eps"])
         return ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
 
     def forward(self, x):
@@ -487,12 +535,9 @@ class LlamaDecoder:
 
     def next_token(self, hidden_row):
         """lm_head + argmax (or, sampling, the warpers + the draw of step *step_dev) of one final-norm row -> tok_dev (device int64[1])."""
-        if (self.w8 or self.w4) and hidden_row.shape[0] == 1:
-            gemv_w8 = ops.decode_gemm_w8_rows if self.mfma_q else ops.decode_gemv_w8
-            logits = gemv_w8(hidden_row.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
-        elif self.mfma and hidden_row.shape[0] == 1:
-            logits = ops.decode_gemm_rows(hidden_row.contiguous(), self.P.w("lm_head"), out_dtype=torch.float32)
-        else:
+        if hidden_row.shape[0] == 1:
+            logits = self.proj.lm_head(False, self.P, hidden_row)
+        else:       # a block of rows (the prefill's): the GEMM, whatever the decode mode
             logits = ops.linear(hidden_row, self.P.w("lm_head"), out_dtype=torch.float32)
         if self.sampling is not None:
             ops.sample_partial(logits[-1], self.samp_params, self.step_dev, tok=self.tok_dev, fast_ws=self.samp_ws if self.samp_fast else None)
@@ -512,13 +557,7 @@ class LlamaDecoder:
         x = ops.decode_step_begin(self.tok_dev, self.P.t("model.embed_tokens.weight"), self.pos_dev,
                                   rope=(self.cos, self.sin, self.rope_cs) if self.rope_path else None)
         h = self._layers_decode(x, rope_row=False)
-        if self.w8 or self.w4:
-            gemv_w8 = ops.decode_gemm_w8_rows if self.mfma_q else ops.decode_gemv_w8
-            logits = gemv_w8(h.contiguous(), *self.P.fp8("lm_head"), out_dtype=torch.float32)
-        elif self.mfma:
-            logits = ops.decode_gemm_rows(h.contiguous(), self.P.w("lm_head"), out_dtype=torch.float32)
-        else:
-            logits = ops.linear(h, self.P.w("lm_head"), out_dtype=torch.float32)
+        logits = self.proj.lm_head(False, self.P, h)
         if self.sampling is not None:
             ops.sample_partial(logits.view(-1), self.samp_params, self.step_dev, acc=self.amax_acc,     # the same hand-off as argmax_partial
                                fast_ws=self.samp_ws if self.samp_fast else None)
@@ -550,24 +589,27 @@ class LlamaDecoder:
             self._decode_step()
         else:
             if self.graph is None:
-                # one eager step first (lazy weight packing, kernel attribute setup), then rewind and capture
-                snap_tok, snap_pos, snap_step = self.tok_dev.clone(), self.pos_dev.clone(), self.step_dev.clone()
-                self._decode_step()
-                torch.cuda.synchronize()
-                self.tok_dev.copy_(snap_tok)
-                self.pos_dev.copy_(snap_pos)
-                self.step_dev.copy_(snap_step)
-                g = torch.cuda.CUDAGraph()
-                # thread-local capture mode: in multi-GPU runs the RCCL watchdog thread of torch.distributed polls events of
-                # finished collectives; under the default (global) mode such a call from another thread can invalidate the capture
-                with ops.graph_capture(g):      # (thread-local capture mode, cyclic GC held off: ops.graph_capture)
-                    self._decode_step()
-                self.graph = self.graphs[key] = g
-                self.tok_dev.copy_(snap_tok)
-                self.pos_dev.copy_(snap_pos)
-                self.step_dev.copy_(snap_step)
+                self.graph = self.graphs[key] = capture_step(self._decode_step, (self.tok_dev, self.pos_dev, self.step_dev))
             self.graph.replay()
         self.pos += 1
+
+
+def capture_step(step, state):
+    """step() captured into a HIP graph that is returned ready to replay: one eager step first (lazy weight packing, kernel attribute setup), then
+    the state tensors (token, position, step counter) are put back, the step is captured, and they are put back again"""
+    snap = [t.clone() for t in state]
+    step()
+    torch.cuda.synchronize()
+    for t, v in zip(state, snap):
+        t.copy_(v)
+    g = torch.cuda.CUDAGraph()
+    # thread-local capture mode: in multi-GPU runs the RCCL watchdog thread of torch.distributed polls events of finished collectives; under
+    # the default (global) mode such a call from another thread can invalidate the capture (ops.graph_capture, which also holds the cyclic GC off)
+    with ops.graph_capture(g):
+        step()
+    for t, v in zip(state, snap):
+        t.copy_(v)
+    return g
 
 
 class RowsDecode:
@@ -580,11 +622,7 @@ class RowsDecode:
     Two forms of the step, as the decoder's single-row step: the rope path (bf16 head_dim 128: q|k|v + RoPE + append, then vg_decode_attention2_rows;
     kw = dec.kpw2) and the decode_attention path (Phi-3-mini width: q|k|v GEMV, then RoPE + append + attention in vg_decode_attention_rows, whose
     rows pick 64 or 128 keys per workgroup on the device from their own position and dec.kpw_min; kw = ATTN_KW).
-    The projections follow the decoder's decode weights: bf16 (vg_decode_gemv_rows; with cfg["decode_gemv"] = "mfma" vg_decode_gemm_rows, the
-    lm_head included, which is also what the decoder's single-row step then runs), fp8 (the MLP and the lm_head on vg_decode_gemv_w8_rows) or
-    mxfp4 (the MLP on vg_decode_gemv_w4_rows, the lm_head on vg_decode_gemv_w8_rows); the attention projections are bf16 in all three.  With
-    cfg["decode_gemv"] = "mfma_q" the fp8 / mxfp4 projections run on vg_decode_gemm_w8_rows / vg_decode_gemm_w4_rows and the bf16 o (and Phi-3's
-    q|k|v) on vg_decode_gemm_rows — again the kernels of the decoder's single-row step.
+    The projections are the decoder's table (dec.proj, DecodeProjections) asked with rows=True: the weights and formats of the single-row step.
     The step is captured once per sampling route ("greedy" / "sample_fast" / "sample") into a HIP graph; a new seed or temperature is a copy into
     samp_params.  Rows past the live prompts (bucket padding) and retired rows keep computing into their own slots; their tokens are ignored."""
 
@@ -648,48 +686,24 @@ class RowsDecode:
 
     def _step(self):
         d, P, c = self.dec, self.dec.P, self.dec.c
-        gemv = ops.decode_gemm_rows if d.mfma or d.mfma_q else ops.decode_gemv_rows      # decode_gemv = "mfma" / "mfma_q": the kernels of the decoder's single-row step
-        gemv_w8 = ops.decode_gemm_w8_rows if d.mfma_q else ops.decode_gemv_w8_rows
-        gemv_w4 = ops.decode_gemm_w4_rows if d.mfma_q else ops.decode_gemv_w4_rows
+        pr = d.proj
         x = ops.decode_step_begin_rows(self.tok, P.t("model.embed_tokens.weight"), self.pos,
                                        rope=None if self.attn_rows else (d.cos, d.sin, self.rope_cs))
         for i in range(c["num_layers"]):
             l = f"model.layers.{i}."
-            wqkv, _ = P.fused([l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"], stored=l + "self_attn.qkv_proj")
             if self.attn_rows:
-                qkv = gemv(x, wqkv, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
+                qkv = pr.run("qkv", True, P, l, x, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
                 o = ops.decode_attention_rows(qkv, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.cos, d.sin, d.H, d.Hkv, d.hd, self.pos,
                                               self.n_bound, d.hd ** -0.5, self.attn_ws, window=d.window, kpw_min=d.kpw_min)
             else:
-                q = ops.decode_qkv_rope_rows(x, wqkv, P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i], self.row0,
-                                             self.rope_cs, self.pos, d.H, d.Hkv, d.hd)
+                q = ops.decode_qkv_rope_rows(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i],
+                                             self.row0, self.rope_cs, self.pos, d.H, d.Hkv, d.hd)
                 o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
                                                d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
-            x = gemv(o, P.w(l + "self_attn.o_proj"), residual=x)
-            gu_names = [l + "mlp.gate_proj", l + "mlp.up_proj"]
-            if d.w8:
-                # fp8 decode weights: the MLP and (below) the lm_head on the B-row fp8 GEMV, the operands LlamaDecoder._layers_decode picks; the
-                # attention projections stay bf16 as they do there
-                a = gemv_w8(x, *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                            eps=c["rms_eps"], glu=True)
-                x = gemv_w8(a, *P.fp8(l + "mlp.down_proj"), residual=x)
-            elif d.w4:
-                # MXFP4 decode weights: the MLP on the B-row MXFP4 GEMV (packed rows, Params.fp4), the lm_head (below) on the fp8 one — the
-                # operands of the single-row step
-                a = gemv_w4(x, P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), norm_w=P.f32(l + "post_attention_layernorm.weight"),
-                            eps=c["rms_eps"], glu=True)
-                x = gemv_w4(a, P.fp4(l + "mlp.down_proj"), residual=x)
-            else:
-                wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
-                a = gemv(x, wgu, norm_w=P.f32(l + "post_attention_layernorm.weight"), eps=c["rms_eps"], glu=True)
-                x = gemv(a, P.w(l + "mlp.down_proj"), residual=x)
+            x = pr.run("o", True, P, l, o, residual=x)
+            a, x = pr.mlp(True, P, l, x, c["rms_eps"])
         h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])
-        if d.w8 or d.w4:
-            logits = gemv_w8(h, *P.fp8("lm_head"), out_dtype=torch.float32)
-        elif d.mfma:
-            logits = ops.decode_gemm_rows(h, P.w("lm_head"), out_dtype=torch.float32)
-        else:
-            logits = ops.linear(h, P.w("lm_head"), out_dtype=torch.float32)
+        logits = pr.lm_head(True, P, h)
         if self.route == "greedy":
             ops.argmax_partial_rows(logits, self.acc)
         else:
@@ -716,18 +730,7 @@ class RowsDecode:
             return
         g = self.graphs.get(self.route)
         if g is None:
-            # one eager step first (lazy weight packing, kernel attributes), then rewind and capture — as LlamaDecoder.decode_step
-            snap = [t.clone() for t in (self.tok, self.pos, self.step)]
-            self._step()
-            torch.cuda.synchronize()
-            for t, v in zip((self.tok, self.pos, self.step), snap):
-                t.copy_(v)
-            g = torch.cuda.CUDAGraph()
-            with ops.graph_capture(g):
-                self._step()
-            self.graphs[self.route] = g
-            for t, v in zip((self.tok, self.pos, self.step), snap):
-                t.copy_(v)
+            g = self.graphs[self.route] = capture_step(self._step, (self.tok, self.pos, self.step))
         g.replay()
 
     def rows_of(self, b, P, rows):

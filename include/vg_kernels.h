@@ -496,6 +496,27 @@ int vg_upsample2_add(const void* lateral, const void* top, void* y, int B, int H
  * K in {3072, 4096, 8192, 14336}. */
 int vg_decode_gemv_w8(const void* x, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, const float* norm_w,
                       float eps, const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream);
+/* Lossless 13-bit form of bf16 weight rows for the decode GEMV.  Per weight: the byte [sign | c5 | m2] (an OCP e5m2 byte: c = E -
+ * base_row in 1..30 for the biased bf16 exponent E, c = 0 = +-0; m2 = the two high mantissa bits) and the five low mantissa bits; per row the
+ * fp32 scale 2^(base_row - 112).  A row is RAW — not represented; readers take it from the bf16 matrix — when its non-zero exponents span more
+ * than 30 binades, when it holds a denormal, an inf or a NaN, or when its scale is no normal fp32.
+ * Layout: row n = K / 2048 blocks of 3328 bytes at packed + n * vg_decode_pack13_row_bytes(K); block b covers K elements [2048 b, 2048 b + 2048)
+ * as four lane-major planes, 64 x 16 B | 64 x 16 B | 64 x 16 B | 64 x 4 B = dwords H[0..3] | H[4..7] | L[0..3] | L[4] of lane 0..63.  The lane's
+ * 32 weights are i = 8 u + j = element 8 (256 b + 64 u + lane) + j of the row (u < 4, j < 8): high byte in byte i % 4 of H[i / 4], low bits at
+ * bits 5 i .. 5 i + 4 of the 160-bit little-endian string L.
+ * vg_decode_pack13: W bf16 [N, K] (ldw elements, a multiple of 8; 16-byte aligned), K a multiple of 2048 -> packed, scale[N] (1 for a raw row) and
+ * rawflag[N] (1 = raw; a raw row's block holds no meaning).  vg_decode_pack13_row_bytes: 0 for an unsupported K. */
+int64_t vg_decode_pack13_row_bytes(int K);
+int vg_decode_pack13(const void* W, int64_t ldw, int N, int K, uint8_t* packed, float* scale, uint8_t* rawflag, vg_stream_t stream);
+/* the inverse: out bf16 [N, K] (ldo elements) from packed + scale, rows listed in raw[nraw] (int32) copied from W */
+int vg_decode_unpack13(const uint8_t* packed, const float* scale, const int* raw, int nraw, const void* W, int64_t ldw, void* out, int64_t ldo,
+                       int N, int K, vg_stream_t stream);
+/* vg_decode_gemv (bf16 x, bf16 W) streaming the packed form of W instead of W: 13/16 of the bytes, the same bits.  The rows listed in raw[nraw]
+ * are recomputed from W (which must stay the matrix that was packed).  K in {4096, 14336} (vg_decode_gemv_p13_supported), VG_ERR_UNSUPPORTED
+ * otherwise; out_dtype VG_BF16 | VG_F32; x, the norm, glu, R and the epilogue as vg_decode_gemv. */
+int vg_decode_gemv_p13_supported(int K);
+int vg_decode_gemv_p13(const void* x, const void* W, int64_t ldw, const uint8_t* packed, const float* scale, const int* raw, int nraw, void* y,
+                       const float* norm_w, float eps, const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream);
 /* vg_decode_gemv with MXFP4 weights (OCP Microscaling v1.0; cfg decode_weights = "mxfp4", the MLP of the decode step — weight-only
  * quantisation of what R/chat.py:247-272 asks of bitsandbytes' load_in_4bit, in gfx950's own 4-bit format): blocks of 32 consecutive K elements of
  * a weight row share the scale 2^(s - 127) (one e8m0 byte s), the elements are e2m1 codes (bit 3 sign; magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6), element

@@ -16,8 +16,8 @@ def role(name):
     if "decode_gemv_fast_kernel" in name:
         if "short, true," in name or "float, true," in name:
             return "gate|up (norm + SwiGLU)"
-        if name.rstrip(">(DecGemvArgs) ").endswith(", 64"):
-            return "qkv (norm + RoPE + append)"          # r06: the RoPE form (last template argument = D/2)
+        if ", 64>" in name or ", 64, false>" in name:
+            return "qkv (norm + RoPE + append)"          # r06: the RoPE form (template argument RHD = D/2, the last one before P13 came behind it)
         return "down (+ residual)" if ", 7, " in name else "qkv / o"
     return None
 

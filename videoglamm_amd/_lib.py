@@ -44,6 +44,11 @@ def _sig(lib):
         "vg_decode_gemv": ([P, P, L, P, P, F, P, I, I, I, I, I, P], c_int),
         "vg_decode_gemv_w8": ([P, P, L, P, P, P, F, P, I, I, I, I, P], c_int),
         "vg_decode_gemv_w4": ([P, P, L, P, P, P, F, P, I, I, I, I, P], c_int),
+        "vg_decode_pack13_row_bytes": ([I], c_int64),
+        "vg_decode_pack13": ([P, L, I, I, P, P, P, P], c_int),
+        "vg_decode_unpack13": ([P, P, P, I, P, L, P, L, I, I, P], c_int),
+        "vg_decode_gemv_p13_supported": ([I], c_int),
+        "vg_decode_gemv_p13": ([P, P, L, P, P, P, I, P, P, F, P, I, I, I, I, P], c_int),
         "vg_decode_attention_ws_floats": ([I, I, I, I], c_int64),
         "vg_decode_attention": ([P, P, P, P, P, P, I, I, I, I, I, F, P, P, L, I, I, P], c_int),
         "vg_decode_qkv_rope_supported": ([I, I, I, I, I], c_int),

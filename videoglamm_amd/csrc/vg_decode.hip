@@ -61,6 +61,31 @@ __device__ __forceinline__ float dec_dot_w8(const u32x4_t& w, const u32x4_t& x0,
   }
   return s;
 }
+// 13-bit bf16 (vg_decode_pack13): one 16-byte x chunk against the lane's weights 8 U .. 8 U + 7 of a (row, batch) block.  H = the 8 dwords of
+// high bytes [sign | e5 | m2] (weight i in byte i % 4 of H[i / 4]), L = the 160-bit string of low mantissa bits (weight i at bits 5 i .. 5 i + 4).
+// v_cvt_pk_f32_bf8 makes the fp32 sign | code + 112 | m2 << 21 of two weights; the five low bits go under it at fp32 bits 20..16 with one
+// (funnel) shift and one v_and_or.  The operand is the true weight times 2^(112 - base_row), and the fmaf chain is dec_dot<bf16_t>'s.
+template <int U> __device__ __forceinline__ float dec_dot_p13(const uint32_t (&H)[8], const uint32_t (&L)[5], const u32x4_t& x) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  float s = 0.f;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)H[2 * U + h], false), hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)H[2 * U + h], true);
+    const float f[4] = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int j = 4 * h + t, bit = 5 * (8 * U + j), d = bit >> 5, o = bit & 31;
+      uint32_t m;          // the weight's five bits at 20..16 (other bits: neighbours, masked below)
+      if (o <= 16) m = L[d] << (16 - o);
+      else if (o <= 27) m = L[d] >> (o - 16);
+      else m = __builtin_amdgcn_alignbit(L[d < 4 ? d + 1 : d], L[d], o - 16);
+      const float w = __uint_as_float((m & 0x001f0000u) | __float_as_uint(f[t]));
+      const uint32_t xe = x[j >> 1];
+      s = fmaf(w, __uint_as_float((j & 1) ? (xe & 0xffff0000u) : (xe << 16)), s);
+    }
+  }
+  return s;
+}
 template <typename T> __device__ __forceinline__ float dec_round(float v) { return v; }
 template <> __device__ __forceinline__ float dec_round<bf16_t>(float v) { return bf2f(f2bf(v)); }
 
@@ -76,7 +101,18 @@ struct DecGemvArgs {
   // registers with the CURRENT position's cos / sin row (rope_cs: [2][D/2] fp32 at a fixed address, refreshed by vg_decode_advance), q heads go to
   // y, the new key / value rows straight into the caches at *pos_dev
   const float* rope_cs; const int* pos_dev; void* kc; void* vc; int H, Hkv;
+  // 13-bit bf16 weights (vg_decode_gemv_p13): Wp = the packed (row, batch) blocks that are streamed in place of W, wscale = 2^(base_row - 112)
+  // per row (1 for a raw row), raw[nraw] = the rows that are recomputed from W itself
+  const uint8_t* Wp; const int* raw; int nraw;
 };
+
+// Lossless 13-bit bf16 rows.  A weight keeps its sign, its 7 mantissa bits and a 5-bit exponent code c = E - base_row in 1..30 (E the
+// biased bf16 exponent; c = 0 with a zero mantissa = +-0).  A row whose non-zero exponents span more than 30 binades, that holds a denormal, an
+// inf or a NaN, or whose scale 2^(base_row - 112) is no normal fp32 is RAW: its block is not used and the GEMV recomputes it from the bf16 matrix.
+// Layout: per (row, batch of 2048 K elements) one 3328-byte block of four lane-major planes, 64 x 16 B | 64 x 16 B | 64 x 16 B | 64 x 4 B = the
+// dwords H[0..3] | H[4..7] | L[0..3] | L[4] of each lane (dec_dot_p13); the lane's 32 weights are those of its four 16-byte chunks of the bf16 walk,
+// weight 8 u + j = element j of chunk (batch * 256 + u * 64 + lane).
+constexpr int DEC_P13_BLOCK = 3328;
 
 template <typename T, typename TO, bool GLU>
 __device__ __forceinline__ void dec_gemv_store(const DecGemvArgs& p, int pi, float a0, float a1) {
@@ -120,7 +156,16 @@ constexpr int DEC_MAX_PPW = 64;
 // W8: the weights are fp8 (OCP e4m3, one byte each) with a per-row scale; a weight chunk then covers 16 K elements = TWO
 // x chunks, and NB x CPB x 64 counts weight chunks (K = 16 x that).
 // RHD = D/2 > 0: the RoPE form above (pairs (d, d + RHD) of a head instead of adjacent rows)
-template <typename T, typename TO, bool GLU, int NB, int CPB = 4, bool W8 = false, int RHD = 0>
+// P13: the weights stream as 13-bit bf16 blocks (p.Wp, above): a batch of a row is 3 x 16 + 4 bytes per lane instead of 4 x 16, in the same four
+// load instructions, and covers the same K elements in the same (chunk, element) order.  The result has the bits of the bf16 kernel's:
+//   * the decoded operand is the true weight times 2^k, k = 112 - base_row fixed per row, and x is the same, so by induction every partial sum of
+//     the fmaf chain, of the per-chunk adds and of wave_sum is the bf16 kernel's times 2^k: each operation rounds the same significand, as long
+//     as no partial sum, with or without the factor 2^k, is a denormal or overflows;
+//   * the order of operations is the bf16 kernel's: lane, batch, chunk and element walk, one fmaf per weight, one add per chunk, wave_sum;
+//   * the multiplication by 2^-k (p.wscale, a normal fp32 power of two) after wave_sum is exact under the same condition.
+// The condition is a premise on the data (|x| within 2^+-60 is ample); a raw row does not lean on it: it is recomputed (3b below)
+// from the bf16 matrix with the bf16 kernel's own code, and its wscale is 1.
+template <typename T, typename TO, bool GLU, int NB, int CPB = 4, bool W8 = false, int RHD = 0, bool P13 = false>
 __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
   extern __shared__ __attribute__((aligned(16))) char dec_smem[];
   __shared__ float red[4];
@@ -130,7 +175,8 @@ __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
   constexpr int KPC = 16 / sizeof(T);
   constexpr int NWV = KPC / 4;     // float4 loads of norm weight per chunk
   static_assert(!W8 || sizeof(T) == 2, "fp8 weights pair with bf16 activations");
-  constexpr int NCH = NB * CPB * 64 * (W8 ? 2 : 1);   // 16-byte chunks of x (with W8 a weight row has half as many)
+  static_assert(!P13 || (sizeof(T) == 2 && CPB == 4 && !W8 && RHD == 0), "13-bit weights: bf16 rows in batches of four chunks per lane");
+  constexpr int NCH = NB * CPB * 64 * (W8 ? 2 : 1);  // 16-byte chunks of x (with W8 a weight row has half as many)
   constexpr int XN = (NCH + 255) / 256;          // chunks of x per thread (the last one may be partial: NCH % 256 == 128)
   typedef float f32x4_t __attribute__((ext_vector_type(4)));
   u32x4_t* xs = (u32x4_t*)dec_smem;
@@ -162,12 +208,24 @@ __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
     const int pc = min(ipi, npair - 1);                      // clamped: the two prologue issues are unconditional
     const int n0 = RHD > 0 ? (pc / max(RHD, 1)) * (2 * RHD) + pc % max(RHD, 1) : GLU ? pc : 2 * pc;
     const int n1 = RHD > 0 ? n0 + RHD : GLU ? p.N + pc : min(2 * pc + 1, p.N - 1);
-    const u32x4_t* w0 = (const u32x4_t*)(W + (int64_t)n0 * p.ldw) + icb * (64 * CPB) + lane;
-    const u32x4_t* w1 = (const u32x4_t*)(W + (int64_t)n1 * p.ldw) + icb * (64 * CPB) + lane;
+    if constexpr (P13) {                                     // three planes of 16 bytes per lane and one of 4: v[0..2] and v[3][0]
+      const uint8_t* b0 = p.Wp + ((int64_t)n0 * NB + icb) * DEC_P13_BLOCK;
+      const uint8_t* b1 = p.Wp + ((int64_t)n1 * NB + icb) * DEC_P13_BLOCK;
 #pragma unroll
-    for (int u = 0; u < CPB; ++u) {
-      v0[u] = __builtin_nontemporal_load(w0 + u * 64);
-      v1[u] = __builtin_nontemporal_load(w1 + u * 64);
+      for (int u = 0; u < 3; ++u) {
+        v0[u] = __builtin_nontemporal_load((const u32x4_t*)(b0 + u * 1024) + lane);
+        v1[u] = __builtin_nontemporal_load((const u32x4_t*)(b1 + u * 1024) + lane);
+      }
+      v0[3][0] = __builtin_nontemporal_load((const uint32_t*)(b0 + 3072) + lane);
+      v1[3][0] = __builtin_nontemporal_load((const uint32_t*)(b1 + 3072) + lane);
+    } else {
+      const u32x4_t* w0 = (const u32x4_t*)(W + (int64_t)n0 * p.ldw) + icb * (64 * CPB) + lane;
+      const u32x4_t* w1 = (const u32x4_t*)(W + (int64_t)n1 * p.ldw) + icb * (64 * CPB) + lane;
+#pragma unroll
+      for (int u = 0; u < CPB; ++u) {
+        v0[u] = __builtin_nontemporal_load(w0 + u * 64);
+        v1[u] = __builtin_nontemporal_load(w1 + u * 64);
+      }
     }
     if (++icb == NB) { icb = 0; ++ipi; }
   };
@@ -214,8 +272,23 @@ __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
   float a0 = 0.f, a1 = 0.f;
   int cpl = 0, ccb = 0;            // consume cursor (local pair, batch within the pair)
   auto consume = [&](const u32x4_t (&v0)[CPB], const u32x4_t (&v1)[CPB]) {
+    if constexpr (P13) {
+      const uint32_t H0[8] = {v0[0][0], v0[0][1], v0[0][2], v0[0][3], v0[1][0], v0[1][1], v0[1][2], v0[1][3]};
+      const uint32_t H1[8] = {v1[0][0], v1[0][1], v1[0][2], v1[0][3], v1[1][0], v1[1][1], v1[1][2], v1[1][3]};
+      const uint32_t L0[5] = {v0[2][0], v0[2][1], v0[2][2], v0[2][3], v0[3][0]}, L1[5] = {v1[2][0], v1[2][1], v1[2][2], v1[2][3], v1[3][0]};
+      const int wc = ccb * (64 * CPB) + lane;
+      const u32x4_t x0 = xs[wc], x1 = xs[wc + 64], x2 = xs[wc + 128], x3 = xs[wc + 192];
+      a0 += dec_dot_p13<0>(H0, L0, x0);
+      a1 += dec_dot_p13<0>(H1, L1, x0);
+      a0 += dec_dot_p13<1>(H0, L0, x1);
+      a1 += dec_dot_p13<1>(H1, L1, x1);
+      a0 += dec_dot_p13<2>(H0, L0, x2);
+      a1 += dec_dot_p13<2>(H1, L1, x2);
+      a0 += dec_dot_p13<3>(H0, L0, x3);
+      a1 += dec_dot_p13<3>(H1, L1, x3);
+    }
 #pragma unroll
-    for (int u = 0; u < CPB; ++u) {
+    for (int u = 0; u < (P13 ? 0 : CPB); ++u) {
       const int wc = ccb * (64 * CPB) + u * 64 + lane;
       if constexpr (W8) {
         const u32x4_t xa = xs[2 * wc], xb = xs[2 * wc + 1];
@@ -255,6 +328,25 @@ __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
     consume(vb0, vb1);
   } else if (rem == 1) {
     consume(va0, va1);
+  }
+  // ---- 3b. 13-bit weights: the raw rows among this wave's pairs, recomputed from the bf16 matrix in the bf16 kernel's order
+  if constexpr (P13) {
+    for (int r = 0; r < p.nraw; ++r) {
+      const int n = p.raw[r];
+      const int pi = GLU ? (n < p.N ? n : n - p.N) : n >> 1, half = GLU ? (n >= p.N) : (n & 1);
+      if (n < 0 || n >= (GLU ? 2 * p.N : p.N) || pi < p0 || pi >= p0 + np) continue;
+      const u32x4_t* w =(const u32x4_t*)(W + (int64_t)n * p.ldw);
+      float a = 0.f;
+      for (int cb = 0; cb < NB; ++cb) {
+#pragma unroll
+        for (int u = 0; u < CPB; ++u) {
+          const int wc = cb * (64 * CPB) + u * 64 + lane;
+          a += dec_dot<T>(w[wc], xs[wc]);
+        }
+      }
+      a = wave_sum(a);
+      if (lane == 0) res[wave][pi - p0][half] = a;
+    }
   }
   // ---- 4. epilogue: one lane per pair
   if constexpr (RHD > 0) {
@@ -453,6 +545,162 @@ extern "C" int vg_decode_gemv(const void* x, const void* W, int64_t ldw, void* y
 #undef VG_DEC_GEMV
   vg_set_error("vg_decode_gemv: unsupported dtype combination %d -> %d", in_dtype, out_dtype);
   return VG_ERR_UNSUPPORTED;
+}
+
+// ---- 13-bit bf16 rows: packer, unpacker and the GEMV entry point
+// One workgroup per row: the exponent range of the row decides base_row and raw (phase 1), then thread (batch, lane) gathers the lane's 32
+// weights of that batch and writes its 13 dwords into the four planes (phase 2).  A raw row's block is written all the same (codes mod 32).
+__global__ __launch_bounds__(256) void dec_pack13_kernel(const uint16_t* W, int64_t ldw, int K, uint8_t* packed, float* scale, uint8_t* rawflag) {
+  __shared__ int s_min, s_max, s_bad;
+  const int tid = threadIdx.x, row = blockIdx.x, nb = K / 2048;
+  const uint16_t* w = W + (int64_t)row * ldw;
+  if (tid == 0) { s_min = 255; s_max = 0; s_bad = 0; }
+  __syncthreads();
+  int emin = 255, emax = 0, bad = 0;
+  for (int c = tid; c < K / 8; c += 256) {
+    const u32x4_t v = ((const u32x4_t*)w)[c];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t b = (v[j >> 1] >> (16 * (j & 1))) & 0xffffu, E = (b >> 7) & 255u;
+      if (E == 255u || (E == 0u && (b & 127u))) bad = 1;
+      else if (E) { emin = min(emin, (int)E); emax = max(emax, (int)E); }
+    }
+  }
+  atomicMin(&s_min, emin);
+  atomicMax(&s_max, emax);
+  if (bad) atomicOr(&s_bad, 1);
+  __syncthreads();
+  const int base = s_min <= s_max ? s_min - 1 : 112;        // the smallest non-zero exponent takes code 1; a row of zeros: scale 1
+  const bool raw = s_bad || s_max - base > 30 || base > 239;      // 2^(base - 112) = the fp32 with exponent field base + 15: normal up to 254
+  if (tid == 0) {
+    scale[row] = raw ? 1.f : __uint_as_float((uint32_t)(base + 15) << 23);
+    rawflag[row] = raw;
+  }
+  for (int t = tid; t < nb * 64; t += 256) {
+    const int cb = t >> 6, lane = t & 63;
+    uint32_t H[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t L[3] = {0, 0, 0};                               // the 160-bit string, 64 bits at a time
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const u32x4_t v = ((const u32x4_t*)w)[cb * 256 + u * 64 + lane];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = 8 * u + j, bit = 5 * i;
+        const uint32_t b = (v[j >> 1] >> (16 * (j & 1))) & 0xffffu, E = (b >> 7) & 255u;
+        const uint32_t code = E ? (E - (uint32_t)base) & 31u : 0u;
+        H[i >> 2] |= (((b >> 15) << 7) | (code << 2) | ((b >> 5) & 3u)) << (8 * (i & 3));
+        const uint64_t lo5 = b & 31u;
+        L[bit >> 6] |= lo5 << (bit & 63);
+        if ((bit & 63) > 59) L[(bit >> 6) + 1] |= lo5 >> (64 - (bit & 63));
+      }
+    }
+    uint8_t* blk = packed + ((int64_t)row * nb + cb) * DEC_P13_BLOCK;
+    const u32x4_t h0 = {H[0], H[1], H[2], H[3]}, h1 = {H[4], H[5], H[6], H[7]};
+    const u32x4_t l0 = {(uint32_t)L[0], (uint32_t)(L[0] >> 32), (uint32_t)L[1], (uint32_t)(L[1] >> 32)};
+    ((u32x4_t*)blk)[lane] = h0;
+    ((u32x4_t*)(blk + 1024))[lane] = h1;
+    ((u32x4_t*)(blk + 2048))[lane] = l0;
+    ((uint32_t*)(blk + 3072))[lane] = (uint32_t)L[2];
+  }
+}
+
+// packed + scales + raw list + the original -> bf16 rows (the tests' inverse): a listed row is copied from the original
+__global__ __launch_bounds__(256) void dec_unpack13_kernel(const uint8_t* packed, const float* scale, const int* raw, int nraw, const uint16_t* W,
+                                                           int64_t ldw, uint16_t* out, int64_t ldo, int K) {
+  __shared__ int s_raw;
+  const int tid = threadIdx.x, row = blockIdx.x, nb = K / 2048;
+  if (tid == 0) s_raw = 0;
+  __syncthreads();
+  for (int r = tid; r < nraw; r += 256)
+    if (raw[r] == row) s_raw = 1;
+  __syncthreads();
+  uint16_t* o = out + (int64_t)row * ldo;
+  if (s_raw) {
+    for (int c = tid; c < K / 8; c += 256) ((u32x4_t*)o)[c] = ((const u32x4_t*)(W + (int64_t)row * ldw))[c];
+    return;
+  }
+  const uint32_t base = (__float_as_uint(scale[row]) >> 23) - 15u;
+  for (int t = tid; t < nb * 64; t += 256) {
+    const int cb = t >> 6, lane = t & 63;
+    const uint8_t* blk = packed + ((int64_t)row * nb + cb) * DEC_P13_BLOCK;
+    const u32x4_t h0 = ((const u32x4_t*)blk)[lane], h1 = ((const u32x4_t*)(blk + 1024))[lane], l0 = ((const u32x4_t*)(blk + 2048))[lane];
+    const uint32_t H[8] = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+    const uint64_t L[3] = {l0[0] | ((uint64_t)l0[1] << 32), l0[2] | ((uint64_t)l0[3] << 32), ((const uint32_t*)(blk + 3072))[lane]};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      u32x4_t v = {0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = 8 * u + j, bit = 5 * i;
+        const uint32_t hb = (H[i >> 2] >> (8 * (i & 3))) & 255u, code = (hb >> 2) & 31u;
+        uint64_t lo5 = L[bit >> 6] >> (bit & 63);
+        if ((bit & 63) > 59) lo5 |= L[(bit >> 6) + 1] << (64 - (bit & 63));
+        const uint32_t b = ((hb >> 7) << 15) | ((code ? code + base : 0u) << 7) | ((hb & 3u) << 5) | ((uint32_t)lo5 & 31u);
+        v[j >> 1] |= b << (16 * (j & 1));
+      }
+      ((u32x4_t*)o)[cb * 256 + u * 64 + lane] = v;
+    }
+  }
+}
+
+extern "C" int64_t vg_decode_pack13_row_bytes(int K) { return K > 0 && K % 2048 == 0 ? (int64_t)(K / 2048) * DEC_P13_BLOCK : 0; }
+
+extern "C" int vg_decode_pack13(const void* W, int64_t ldw, int N, int K, uint8_t* packed, float* scale, uint8_t* rawflag, vg_stream_t stream) {
+  VG_CHECK(W && packed && scale && rawflag && N > 0, VG_ERR_ARG, "vg_decode_pack13: bad args N=%d K=%d", N, K);
+  VG_CHECK(vg_decode_pack13_row_bytes(K) && ldw % 8 == 0 && ldw >= K, VG_ERR_ARG, "vg_decode_pack13: K=%d must be a multiple of 2048, ldw=%lld of 8",
+           K, (long long)ldw);
+  VG_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)packed & 15) == 0, VG_ERR_ARG, "vg_decode_pack13: W/packed must be 16-byte aligned");
+  dec_pack13_kernel<<<N, 256, 0, (hipStream_t)stream>>>((const uint16_t*)W, ldw, K, packed, scale, rawflag);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_decode_unpack13(const uint8_t* packed, const float* scale, const int* raw, int nraw, const void* W, int64_t ldw, void* out,
+                                  int64_t ldo, int N, int K, vg_stream_t stream) {
+  VG_CHECK(packed && scale && W && out && N > 0 && nraw >= 0 && (raw || !nraw), VG_ERR_ARG, "vg_decode_unpack13: bad args N=%d K=%d nraw=%d", N, K, nraw);
+  VG_CHECK(vg_decode_pack13_row_bytes(K) && ldw % 8 == 0 && ldw >= K && ldo % 8 == 0 && ldo >= K, VG_ERR_ARG,
+           "vg_decode_unpack13: K=%d must be a multiple of 2048, ldw=%lld / ldo=%lld of 8", K, (long long)ldw, (long long)ldo);
+  VG_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)out & 15) == 0, VG_ERR_ARG,
+           "vg_decode_unpack13: W/packed/out must be 16-byte aligned");
+  dec_unpack13_kernel<<<N, 256, 0, (hipStream_t)stream>>>(packed, scale, raw, nraw, (const uint16_t*)W, ldw, (uint16_t*)out, ldo, K);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_decode_gemv_p13_supported(int K) { return K == 4096 || K == 14336; }
+
+template <typename TO, bool GLU>
+static int launch_decode_gemv_p13(DecGemvArgs p, hipStream_t st) {
+  const int npair = GLU ? p.N : (p.N + 1) / 2;
+  const int maxw = 256 * 2 * 4;                              // launch_decode_gemv's split (two workgroups per CU)
+  int ppw = (npair + maxw - 1) / maxw;
+  for (int c = ppw; c <= 2 * ppw; ++c)
+    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
+  if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
+  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
+  p.ppw = ppw;
+  const size_t lds = (size_t)p.K * 2;
+  if (p.K == 4096) decode_gemv_fast_kernel<bf16_t, TO, GLU, 2, 4, false, 0, true><<<blocks, 256, lds, st>>>(p);
+  else decode_gemv_fast_kernel<bf16_t, TO, GLU, 7, 4, false, 0, true><<<blocks, 256, lds, st>>>(p);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_decode_gemv_p13(const void* x, const void* W, int64_t ldw, const uint8_t* packed, const float* scale, const int* raw, int nraw,
+                                  void* y, const float* norm_w, float eps, const void* R, int N, int K, int glu, int out_dtype, vg_stream_t stream) {
+  VG_CHECK(x && W && packed && scale && y && N > 0 && nraw >= 0 && (raw || !nraw), VG_ERR_ARG, "vg_decode_gemv_p13: bad args N=%d K=%d nraw=%d", N, K, nraw);
+  VG_CHECK(vg_decode_gemv_p13_supported(K), VG_ERR_UNSUPPORTED, "vg_decode_gemv_p13: K=%d is not one of the supported row lengths (4096, 14336)", K);
+  VG_CHECK(ldw % 8 == 0 && ldw >= K, VG_ERR_ARG, "vg_decode_gemv_p13: ldw=%lld must be a multiple of 8 and at least K=%d", (long long)ldw, K);
+  VG_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)norm_w & 15) == 0, VG_ERR_ARG,
+           "vg_decode_gemv_p13: x/W/packed/norm_w must be 16-byte aligned");
+  VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemv_p13: bad out_dtype %d", out_dtype);
+  DecGemvArgs p{x, W, y, norm_w, R, N, K, ldw, eps, 1, scale};
+  p.Wp = packed;
+  p.raw = raw;
+  p.nraw = nraw;
+  hipStream_t st = (hipStream_t)stream;
+  if (out_dtype == VG_BF16) return glu ? launch_decode_gemv_p13<bf16_t, true>(p, st) : launch_decode_gemv_p13<bf16_t, false>(p, st);
+  return glu ? launch_decode_gemv_p13<float, true>(p, st) : launch_decode_gemv_p13<float, false>(p, st);
 }
 
 // q|k|v projection of the new token with RMSNorm in front and RoPE + KV-cache append behind it (r06): the rows of a rotate-half pair

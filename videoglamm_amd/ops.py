@@ -583,12 +583,65 @@ def _decode_proj(entry, x, w, mid, norm_w, eps, residual, glu, out_dtype, out, x
     return y
 
 
-def decode_gemv(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+def decode_gemv(x, w, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None, p13=None):
     """Decode-step projection of ONE row: y[N] = rmsnorm(x; norm_w, eps) (or x) @ w^T, optional SwiGLU over w = [gate|up]
-    rows and optional residual — HF LlamaRMSNorm + nn.Linear (+ LlamaMLP act) in one launch (vg_decode_gemv)."""
+    rows and optional residual — HF LlamaRMSNorm + nn.Linear (+ LlamaMLP act) in one launch (vg_decode_gemv).
+    p13 = decode_pack13(w): the launch streams those 13-bit rows instead of w (vg_decode_gemv_p13) and gives the same bits."""
     K = x.shape[-1]
     assert x.numel() == K and x.is_contiguous() and w.stride(1) == 1 and w.shape[1] == K
+    if p13 is not None:
+        return decode_gemv_p13(x, w, *p13, norm_w=norm_w, eps=eps, residual=residual, glu=glu, out_dtype=out_dtype, out=out)
     return _decode_proj("vg_decode_gemv", x, w, (), norm_w, eps, residual, glu, out_dtype, out, x_code=True)
+
+
+P13_RAW_CAP = 256      # a matrix with more than 1 / P13_RAW_CAP of its rows raw is not packed (decode_pack13)
+
+
+def decode_pack13(w, raw_cap=True):
+    """bf16 [N,K] weight (K a multiple of 2048) -> (packed uint8 [N, K/2048 * 3328], fp32 [N] row scales, int32 [nraw] ascending raw rows): the
+    lossless 13-bit rows decode_gemv_p13 streams (vg_decode_pack13, include/vg_kernels.h).  None when raw_cap and more than 1/256 of the rows are raw:
+    such a matrix stays on decode_gemv.  One-time load work; reads the raw flags back (a sync)."""
+    lib = _lib.load()
+    N, K = w.shape
+    rb = lib.vg_decode_pack13_row_bytes(int(K))
+    assert w.dtype == torch.bfloat16 and w.stride(1) == 1 and rb, "decode_pack13: bf16 rows, K a multiple of 2048"
+    packed = torch.empty(N, rb, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    flag = torch.empty(N, dtype=torch.uint8, device=w.device)
+    _lib.check(lib.vg_decode_pack13(_p(w), w.stride(0), N, K, _p(packed), _p(scale), _p(flag), _stream()), "vg_decode_pack13")
+    raw = flag.nonzero().view(-1).to(torch.int32)
+    if raw_cap and raw.numel() * P13_RAW_CAP > N:
+        return None
+    return packed, scale, raw
+
+
+def decode_unpack13(packed, scale, raw, w):
+    """the bf16 [N,K] matrix that (packed, scale, raw) of decode_pack13(w) stand for: rows listed in raw come from w (vg_decode_unpack13)"""
+    lib = _lib.load()
+    N, K = w.shape
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.shape == (N, lib.vg_decode_pack13_row_bytes(int(K)))
+    assert scale.dtype == torch.float32 and scale.numel() == N and scale.is_contiguous() and raw.dtype == torch.int32 and raw.is_contiguous()
+    assert w.dtype == torch.bfloat16 and w.stride(1) == 1
+    out = torch.empty(N, K, dtype=torch.bfloat16, device=w.device)
+    rc = lib.vg_decode_unpack13(_p(packed), _p(scale), _p(raw if raw.numel() else None), raw.numel(), _p(w), w.stride(0), _p(out), K, N, K, _stream())
+    _lib.check(rc, "vg_decode_unpack13")
+    return out
+
+
+def decode_gemv_p13_supported(K):
+    """True when decode_gemv_p13 has the row length K (vg_decode_gemv_p13_supported: 4096, 14336)"""
+    return bool(_lib.load().vg_decode_gemv_p13_supported(int(K)))
+
+
+def decode_gemv_p13(x, w, packed, scale, raw, norm_w=None, eps=0.0, residual=None, glu=False, out_dtype=None, out=None):
+    """decode_gemv(x, w, ...) bit for bit, streaming decode_pack13(w)'s 13-bit rows instead of w (vg_decode_gemv_p13): x bf16 [1,K]; the rows in
+    raw are recomputed from w."""
+    K = x.shape[-1]
+    assert x.dtype == torch.bfloat16 and x.numel() == K and x.is_contiguous() and w.dtype == torch.bfloat16 and w.stride(1) == 1 and w.shape[1] == K
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.shape == (w.shape[0], K // 2048 * 3328)
+    assert scale.dtype == torch.float32 and scale.numel() == w.shape[0] and scale.is_contiguous() and raw.dtype == torch.int32 and raw.is_contiguous()
+    mid = (_p(packed), _p(scale), _p(raw if raw.numel() else None), raw.numel())
+    return _decode_proj("vg_decode_gemv_p13", x, w, mid, norm_w, eps, residual, glu, out_dtype, out)
 
 
 def quantize_fp8_rows(w):

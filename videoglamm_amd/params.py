@@ -96,6 +96,19 @@ class Params:
             return ops.mxfp4_pack(*ops.quantize_mxfp4_rows(w))
         return self._get(("fp4",) + tuple(names), make)
 
+    def p13(self, names, stored=None):
+        """fused()/w() of the named bf16 weights as lossless 13-bit rows for the single-row decode GEMV (ops.decode_pack13): (packed, scales, raw
+        rows), or None for a matrix over the raw-row cap (it stays on the bf16 kernel).  Made once and kept beside the bf16 weight, which the
+        prefill, the batched steps and the raw rows go on reading."""
+        from . import ops
+
+        names = [names] if isinstance(names, str) else list(names)
+
+        def make():
+            w = self.w(names[0]) if len(names) == 1 and stored is None else self.fused(names, stored=stored)[0]
+            return ops.decode_pack13(w)
+        return self._get(("p13",) + tuple(names), make)
+
     # ---- convolutions as GEMMs
     def conv_w(self, name):
         """Conv2d [Cout,Cin,kh,kw] (or Conv3d with kt=1) -> [Cout, (ky*kw+kx)*Cin + c] padded (vg_im2col column order)."""

@@ -214,16 +214,24 @@ class DecodeProjections:
     Entry point: KERNELS[fmt], picked by cfg["decode_gemv"] and by whether the step is the single-row one (LlamaDecoder) or the B-row one
     (RowsDecode, rows=True): under "mfma" / "mfma_q" both steps run the MFMA B-row kernels (B = 1 in the single-row step).  The bf16 lm_head of
     the VALU modes is a plain ops.linear.  Entries are held as names and looked up in ops at call time.
+    self.pack: the bf16 MLP roles whose VALU single-row step hands ops.decode_gemv the lossless 13-bit rows of the same weights to stream
+    (p13=; VG_DECODE_PACK): entry point, stored form and bits stay decode_gemv's on the bf16 weight, so the B-row step, weights()
+    and covered() see no difference.
     gate_up runs behind the fused post_attention_layernorm with SwiGLU, qkv behind input_layernorm; o and down add the residual; the lm_head
     gives fp32 logits."""
     #          fmt      VALU single-row    VALU B-row             MFMA, either step
     KERNELS = {"bf16": ("decode_gemv",    "decode_gemv_rows",    "decode_gemm_rows"),
                "w8":   ("decode_gemv_w8", "decode_gemv_w8_rows", "decode_gemm_w8_rows"),
                "w4":   ("decode_gemv_w4", "decode_gemv_w4_rows", "decode_gemm_w4_rows")}
+    # (role, K) whose VALU single-row decode_gemv streams the 13-bit rows of its bf16 weight (DESIGN 8b).  VG_DECODE_PACK unset: these, the shapes
+    # where that measured faster than streaming the bf16 weight (DESIGN 0a); "1": wherever the kernel exists; "0": nowhere
+    PACK_DEFAULT = {("gate_up", 4096), ("down", 14336)}
+    PACK_K = (4096, 14336)       # vg_decode_gemv_p13_supported, held here so that the table stays pure
 
-    def __init__(self, decode_gemv, decode_weights, hidden=0, ffn=0, vocab=0, qkv=0, attn=None, step=None):
+    def __init__(self, decode_gemv, decode_weights, hidden=0, ffn=0, vocab=0, qkv=0, attn=None, step=None, env=None, pack=True):
         """decode_gemv / decode_weights: the cfg values; hidden, ffn, vocab, qkv (rows of q|k|v), attn (heads x head_dim: o's K; default hidden):
-        the widths weights() reports; step: "rope" | "attention" | None as decode_gemv_mode's.  Pure: no device work."""
+        the widths weights() reports; step: "rope" | "attention" | None as decode_gemv_mode's; env: the environment (VG_DECODE_PACK; default
+        os.environ); pack=False: no 13-bit rows (a model that is not bf16).  Pure: no device work."""
         self.mfma = decode_gemv in ("mfma", "mfma_q")
         mlp = {"fp8": "w8", "mxfp4": "w4"}.get(decode_weights, "bf16")
         self.fmt = dict(qkv="bf16", o="bf16", gate_up=mlp, down=mlp, lm_head="bf16" if mlp == "bf16" else "w8")
@@ -232,6 +240,11 @@ class DecodeProjections:
         self.shape = dict(o=(hidden, attn, False), gate_up=(ffn, hidden, True), down=(hidden, ffn, False), lm_head=(vocab, hidden, False))
         if step == "attention":
             self.shape["qkv"] = (qkv, hidden, True)
+        # the MLP roles whose single-row step runs on the 13-bit rows: VALU mode, bf16 decode weights, Llama widths (both row lengths covered)
+        knob = (os.environ if env is None else env).get("VG_DECODE_PACK", "")
+        self.pack = {r for r in ("gate_up", "down")
+                     if pack and mlp == "bf16" and not self.mfma and knob != "0" and {hidden, ffn} == set(self.PACK_K)
+                     and (knob == "1" or (r, self.shape[r][1]) in self.PACK_DEFAULT)}
 
     def entry(self, role, rows=False):
         """the name of the ops function that runs `role` in the single-row (rows=False) or the B-row step"""
@@ -249,8 +262,10 @@ class DecodeProjections:
         sup = getattr(ops, self.KERNELS[fmt][2 if self.mfma else int(bool(rows))] + "_supported")
         return sup(N, K) if self.mfma else sup(K)
 
-    def operands(self, P, role, l=""):
-        """the weight operands of `role` in layer prefix l ("model.layers.3."), in the role's stored form: one tensor, or fp8's (codes, scales)"""
+    def operands(self, P, role, l="", packed=False):
+        """the weight operands of `role` in layer prefix l ("model.layers.3."), in the role's stored form: one tensor, or fp8's (codes, scales);
+        packed (a role of self.pack in the single-row step): the bf16 tensor, then its 13-bit rows, scales and raw rows — or the bf16 tensor alone
+        where the matrix is over the raw-row cap"""
         names, stored = {"qkv": ([l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"], l + "self_attn.qkv_proj"),
                          "o": (l + "self_attn.o_proj", None), "gate_up": ([l + "mlp.gate_proj", l + "mlp.up_proj"], l + "mlp.gate_up_proj"),
                          "down": (l + "mlp.down_proj", None), "lm_head": ("lm_head", None)}[role]
@@ -259,10 +274,14 @@ class DecodeProjections:
             return P.fp8(names, stored=stored)
         if fmt == "w4":
             return (P.fp4(names, stored=stored),)
-        return (P.w(names) if stored is None else P.fused(names, stored=stored)[0],)
+        w = P.w(names) if stored is None else P.fused(names, stored=stored)[0]
+        return (w,) + ((P.p13(names, stored=stored) or ()) if packed else ())
 
     def run(self, role, rows, P, l, x, **kw):
         """launch `role` on x: kw = the entry point's norm_w / eps / glu / residual / out_dtype"""
+        if role in self.pack and not rows:
+            w, *p13 = self.operands(P, role, l, packed=True)
+            return getattr(ops, self.entry(role, rows))(x, w, p13=tuple(p13) or None, **kw)
         return getattr(ops, self.entry(role, rows))(x, *self.operands(P, role, l), **kw)
 
     def mlp(self, rows, P, l, x, eps):
@@ -363,7 +382,7 @@ class LlamaDecoder:
             step = "attention"
         head = params.sd.get("lm_head.weight")       # (a decoder that only prefills may come without one)
         self.proj = DecodeProjections(c.get("decode_gemv"), c.get("decode_weights"), hidden=self.D, ffn=ffn, vocab=0 if head is None else head.shape[0],
-                                      qkv=(self.H + 2 * self.Hkv) * self.hd, attn=self.H * self.hd, step=step)
+                                      qkv=(self.H + 2 * self.Hkv) * self.hd, attn=self.H * self.hd, step=step, pack=dt == torch.bfloat16)
         mode = decode_gemv_mode(c.get("decode_gemv"), c.get("decode_weights"), dt, os.environ, step,
                                 [(N, K) for N, K, _, _ in self.proj.weights(quantised=False)], ops.decode_gemm_rows_supported,
                                 quant_projections=self.proj.weights(quantised=True),

@@ -198,7 +198,22 @@ int vg_decode_attention(const void* qkv, void* k_cache, void* v_cache, const flo
                         void* out, int H, int Hkv, int D, int max_len, int window, float scale, const int* pos_dev,
                         float* workspace, int64_t ws_floats, int keys_per_wg, int dtype, vg_stream_t stream);
 
-/* r06 — the decode step with the RoPE in the projection and the attention as a wave-private flash pass (bf16, head_dim 128):
+/* The fp8 K/V cache of the decode step.  Format: OCP e4m3 (torch.float8_e4m3fn), one byte per element, NO scale; layout
+ *   [max_len, Hkv, D] uint8 — the bf16 cache's layout with one-byte elements.  The value quantised is the bf16 value the bf16 cache would have held,
+ *   clamped to +-448 in fp32 and rounded to nearest even: bit for bit x.float().clamp(-448, 448).to(torch.float8_e4m3fn); a NaN stays a NaN code.
+ *   (Premise: K after RoPE and V are O(1) - O(100); magnitudes above 448 saturate, magnitudes of 2^-10 and below flush to zero.)
+ * vg_kv_quantize_fp8: dst[i] = that code of src[i] (bf16), i < n; src / dst 4-byte aligned.  Used after a prefill on the rows it wrote.
+ * vg_decode_attention_kv8: vg_decode_attention (same arguments, same workspace) with bf16 qkv / out and uint8 caches (8-byte aligned).  Every sum runs
+ *   in the bf16 kernel's order on the exactly converted codes, so the result is bit-identical to vg_decode_attention on the dequantised caches.  The
+ *   new token's key / value take part in their own step unquantised; the row appended at *pos_dev is their quantised form.  Shapes: dtype VG_BF16,
+ *   H / Hkv in {1, 2, 4, 8}, D % 8 == 0, D <= 256 (vg_decode_attention_kv8_supported); keys_per_wg as vg_decode_attention. */
+int vg_kv_quantize_fp8(const void* src, uint8_t* dst, int64_t n, vg_stream_t stream);
+int vg_decode_attention_kv8_supported(int H, int Hkv, int D, int dtype);
+int vg_decode_attention_kv8(const void* qkv, void* k_cache, void* v_cache, const float* cos, const float* sin, void* out, int H, int Hkv, int D,
+                            int max_len, int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg,
+                            int dtype, vg_stream_t stream);
+
+/* r06— the decode step with the RoPE in the projection and the attention as a wave-private flash pass (bf16, head_dim 128):
  * vg_decode_qkv_rope: q|k|v projection of the new token (RMSNorm fused as in vg_decode_gemv) with rotate-half RoPE of the q and k heads and the
  *   KV-cache append in the GEMV's epilogue: q_out [H*D] receives the rotated query heads, k_cache / v_cache ([max_len,Hkv,D]) row *pos_dev the
  *   rotated key / the value row.  rope_cs: fp32 [2][D/2] = cos row | sin row of position *pos_dev (kept current by vg_decode_advance).
@@ -318,6 +333,14 @@ int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const void* k_cache
                              int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out, int H, int Hkv, int D,
                              int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace, int64_t ws_floats, int B, int dtype,
                              vg_stream_t stream);
+/* vg_decode_attention_rows_kv8: vg_decode_attention_rows on the fp8 K/V format above — the shared caches AND the slots hold e4m3 codes (uint8);
+ *   slot_stride is in elements, which are bytes.  Same arguments, workspace and shapes (bf16 qkv / out, MHA, head_dim 96); row b is bit-identical to
+ *   vg_decode_attention_kv8 on that row alone with the whole cache in one array. */
+int vg_decode_attention_rows_kv8_supported(int H, int Hkv, int D, int dtype);
+int vg_decode_attention_rows_kv8(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots, void* v_slots,
+                                 int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out, int H, int Hkv, int D,
+                                 int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace, int64_t ws_floats, int B,
+                                 int dtype, vg_stream_t stream);
 /* Sampled decoding (csrc/vg_sample.hip): HF's Temperature -> TopK -> TopP warpers and the draw on one fp32 logits row x[n]
  *   (n < 2^22), one launch.  params: the 24-byte device block {float T; float p; int k; int pad; uint64 seed} (k = 0: no top-k; p = 1: no top-p).
  * vg_sample_partial — acc[0] = the drawn entry's packed (ordered value bits, ~index) key, the hand-off vg_argmax_partial leaves, so

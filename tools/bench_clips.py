@@ -15,11 +15,13 @@ the modes alternate inside each repetition (loop, clips and the replayed step of
 --decode-weights bf16 fp8 mxfp4: cfg["llm"]["decode_weights"]; every valid (decode_gemv, decode_weights) pair is one model and one line
 ("decode_weights" in the record), all alternating inside each repetition; an invalid pair (mfma with fp8 / mxfp4, mfma_q with bf16) is skipped
 with a printed line.
+--kv-cache bf16 fp8: cfg["llm"]["kv_cache"]; each value is one more model per pair ("kv_cache" in the record), alternating with the
+others inside each repetition.  "slot_bytes"[B]: the bytes of the batched state's K / V slots (RowsDecode.ks + vs) behind that B.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 12's table lives in profiles/).
 
     python tools/bench_clips.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8 16] [--reps 3] [--warmup 1] [--branch framewise]
                                  [--sample k50 k0] [--decode-gemv valu mfma mfma_q] [--decode-weights bf16 fp8 mxfp4]
-                                 [--out FILE]
+                                 [--kv-cache bf16 fp8] [--out FILE]
 """
 import argparse
 import json
@@ -50,8 +52,17 @@ def once(fn):
 
 def pairs(args):
     """the valid (decode_gemv, decode_weights) pairs of the two option lists: mfma streams bf16 weights, mfma_q fp8 / mxfp4 (vlm.decode_gemv_mode)"""
-    return [(dg, dw) for dw in args.decode_weights for dg in args.decode_gemv
+    return [(dg, dw, kv) for dw in args.decode_weights for dg in args.decode_gemv for kv in args.kv_cache
             if not (dg == "mfma" and dw != "bf16") and not (dg == "mfma_q" and dw == "bf16")]
+
+
+def slot_bytes(model):
+    """bytes of the K / V slots of the batched state the last inference_clips() call decoded on (None: it ran the plain loop)"""
+    rows = getattr(getattr(model.P, "_decoder", None), "_rows", None)
+    if not rows:
+        return None
+    r = next(iter(rows.values()))
+    return sum(t.numel() * t.element_size() for t in r.ks + r.vs)
 
 
 def run(llm, mode, args, device):
@@ -59,12 +70,14 @@ def run(llm, mode, args, device):
     cfg["forced_tokens"] = {8: cfg["seg_token_idx"]}
     sd = synth.device_state_dict(synth.manifest(cfg), device, torch.bfloat16)
     models = {}
-    for dg, dw in pairs(args):           # one model per (decode mode, decode weights) on the same weight tensors
+    for dg, dw, kv in pairs(args):       # one model per (decode mode, decode weights, K/V cache) on the same weight tensors
         extra = dict(decode_gemv=dg) if dg != "valu" else {}
         if dw != "bf16":
             extra["decode_weights"] = dw
+        if kv != "bf16":
+            extra["kv_cache"] = kv
         c = dict(cfg, llm=dict(cfg["llm"], **extra)) if extra else cfg
-        models[(dg, dw)] = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, c, torch_dtype=torch.bfloat16, device=device))
+        models[(dg, dw, kv)] = synth.install_forced_tokens(VideoGLaMMForCausalLM(sd, c, torch_dtype=torch.bfloat16, device=device))
     g = torch.Generator().manual_seed(1234)
     te, S = 16, cfg["sam2"]["image_size"]
     iv, cl = cfg["iv2"]["img_size"], cfg["clip"]["img_size"]
@@ -76,9 +89,9 @@ def run(llm, mode, args, device):
     rest = ([(1024, 1024)], [(args.src, args.src)])
     video = args.branch == "video"
     kw = dict(max_new_tokens=args.max_new_tokens, use_sam2_video_branch=video, **SAMPLING[mode])
-    recs = {dg: dict(llm=llm, mode=mode, decode_gemv=dg[0], decode_weights=dg[1], branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
+    recs = {dg: dict(llm=llm, mode=mode, decode_gemv=dg[0], decode_weights=dg[1], kv_cache=dg[2], branch=args.branch, frames=args.frames, max_new_tokens=args.max_new_tokens, reps=args.reps,
                      clips_ms={}, loop_ms={}, clips_spread={}, loop_spread={}, clips_ms_per_clip={}, loop_ms_per_clip={}, rows_step_ms={},
-                     rows_step_spread={}) for dg in models}
+                     rows_step_spread={}, slot_bytes={}) for dg in models}
     spread = lambda v: [round(min(v), 4), round(max(v), 4)]              # noqa: E731
     for B in args.batches:
         clips = [(images, context, sam, x[None], *rest) for x in prompts[:B]]
@@ -90,6 +103,7 @@ def run(llm, mode, args, device):
                 torch.manual_seed(100 + r)
                 b = once(lambda: model.inference_clips(clips, **kw))
                 st = rows_step_ms(model) if B > 1 else None
+                recs[dg]["slot_bytes"][B] = slot_bytes(model) if B > 1 else None
                 if r >= args.warmup:
                     tl[dg].append(a)
                     tb[dg].append(b)
@@ -131,6 +145,8 @@ def main():
                     help="cfg['llm']['decode_gemv']; several: the modes alternate inside each repetition, one line per mode")
     ap.add_argument("--decode-weights", nargs="+", default=["bf16"], choices=["bf16", "fp8", "mxfp4"],
                     help="cfg['llm']['decode_weights']; every valid pair with --decode-gemv is one model, invalid pairs are skipped")
+    ap.add_argument("--kv-cache", nargs="+", default=["bf16"], choices=["bf16", "fp8"],
+                    help="cfg['llm']['kv_cache']; each value is one more model per (decode_gemv, decode_weights) pair")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
@@ -138,7 +154,7 @@ def main():
     modes = ([] if args.no_greedy else ["greedy"]) + list(args.sample or [])
     for dw in args.decode_weights:
         for dg in args.decode_gemv:
-            if (dg, dw) not in pairs(args):
+            if (dg, dw, args.kv_cache[0]) not in pairs(args):
                 print(f"# skipped: decode_gemv = {dg} does not combine with decode_weights = {dw}", flush=True)
     for llm in args.llm:
         for mode in modes:

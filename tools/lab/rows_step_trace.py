@@ -1,6 +1,7 @@
 """Kernel-trace driver of the batched decode step: 8 prompts through prompts.generate_prompts at full Phi-3-mini width (32 layers, bf16 synthetic weights), prefix P = 1700 rows,
 then 24 replayed B = 8 batched steps (the dispatches a kernel trace then cuts out: the last 24 steps).
---decode-weights fp8: the step with fp8 decode weights (the MLP and the lm_head on vg_decode_gemv_w8_rows)."""
+--decode-weights fp8: the step with fp8 decode weights (the MLP and the lm_head on vg_decode_gemv_w8_rows).
+--kv-cache fp8: the step on the e4m3 K/V cache (vg_decode_attention_rows_kv8, uint8 prefix and slots)."""
 import argparse
 import os
 import sys
@@ -15,6 +16,7 @@ from videoglamm_amd.prompts import generate_prompts  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"])
+ap.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8"])
 args = ap.parse_args()
 torch.set_grad_enabled(False)
 
@@ -33,6 +35,8 @@ man = {k: v for k, v in synth.vlm_manifest(full).items()
        if k.startswith(("model.layers.", "model.norm", "model.embed_tokens", "lm_head", "model.text_hidden_fcs"))}
 P = Params(synth.device_state_dict(man, dev, torch.bfloat16), dev, torch.bfloat16)
 c = full["llm"] if args.decode_weights == "bf16" else dict(full["llm"], decode_weights="fp8")
+if args.kv_cache == "fp8":
+    c = dict(c, kv_cache="fp8")
 g = torch.Generator().manual_seed(1)
 nvis = 1697
 visual = (torch.randn(nvis, c["hidden"], generator=g) * 0.5).to(torch.bfloat16).to(dev)
@@ -41,7 +45,8 @@ ids = [torch.cat([head, torch.randint(3, c["vocab"] - 2, (30,), generator=g)]) f
 cfg = dict(llm=c, seg_token_idx=full["seg_token_idx"])
 generate_prompts(P, cfg, Towers(visual), None, None, ids, 32)
 rows = next(iter(P._decoder._rows.values()))
-print(f"row0 {rows.row0} n_bound {rows.n_bound} start_pos {rows.start_pos} B {rows.B} attn_rows {rows.attn_rows}", flush=True)
+print(f"row0 {rows.row0} n_bound {rows.n_bound} start_pos {rows.start_pos} B {rows.B} attn_rows {rows.attn_rows} kv_cache {args.kv_cache} "
+      f"slot bytes {sum(t.numel() * t.element_size() for t in rows.ks + rows.vs)}", flush=True)
 rows.set_positions(rows.start_pos)
 rows.decode_step()
 torch.cuda.synchronize()

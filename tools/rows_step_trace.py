@@ -1,7 +1,7 @@
 """The replayed batched decode step under rocprofv3 --kernel-trace --stats, and the per-kernel table of its dispatches.
 
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/rows_step_trace.py run [--llm llama3-8b] [--batch 16] [--decode-gemv mfma | mfma_q]
-                                                                            [--decode-weights fp8 | mxfp4]
+                                                                            [--decode-weights fp8 | mxfp4] [--kv-cache fp8]
     python tools/rows_step_trace.py table DIR/kt_results.db [--steps 24] > profiles/NAME.txt
 
 run:   clips.generate_clips with --batch clips (a visual block of 1694 rows each, questions of 30..45 ids, 4 new tokens) at the LLM's full depth
@@ -31,6 +31,8 @@ def run(args):
         cfg["llm"] = dict(cfg["llm"], decode_gemv=args.decode_gemv)
     if args.decode_weights != "bf16":
         cfg["llm"] = dict(cfg["llm"], decode_weights=args.decode_weights)
+    if args.kv_cache != "bf16":
+        cfg["llm"] = dict(cfg["llm"], kv_cache=args.kv_cache)
     man = {k: v for k, v in synth.manifest(cfg).items() if k.startswith(("model.layers.", "model.norm", "model.embed_tokens", "lm_head", "model.text_hidden_fcs"))}
     P = Params(synth.device_state_dict(man, device, torch.bfloat16), device, torch.bfloat16)
     g = torch.Generator().manual_seed(7)
@@ -51,7 +53,7 @@ def run(args):
     for _ in range(args.steps):
         step()
     torch.cuda.synchronize()
-    print(f"llm {args.llm} decode_gemv {args.decode_gemv} decode_weights {args.decode_weights} batch {args.batch}: {(time.perf_counter() - t) * 1000.0 / args.steps:.3f} ms per replayed step "
+    print(f"llm {args.llm} decode_gemv {args.decode_gemv} decode_weights {args.decode_weights} kv_cache {args.kv_cache} batch {args.batch}: {(time.perf_counter() - t) * 1000.0 / args.steps:.3f} ms per replayed step "
           f"({args.steps} steps)", flush=True)
 
 
@@ -98,6 +100,7 @@ def main():
     r.add_argument("--batch", type=int, default=16)
     r.add_argument("--decode-gemv", default="valu", choices=["valu", "mfma", "mfma_q"])
     r.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"], help="mfma_q pairs with fp8 / mxfp4, mfma with bf16")
+    r.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8"], help="cfg['llm']['kv_cache'] (DESIGN 8c)")
     r.add_argument("--steps", type=int, default=24)
     t = sub.add_parser("table")
     t.add_argument("db")

@@ -51,6 +51,9 @@ def _sig(lib):
         "vg_decode_gemv_p13": ([P, P, L, P, P, P, I, P, P, F, P, I, I, I, I, P], c_int),
         "vg_decode_attention_ws_floats": ([I, I, I, I], c_int64),
         "vg_decode_attention": ([P, P, P, P, P, P, I, I, I, I, I, F, P, P, L, I, I, P], c_int),
+        "vg_kv_quantize_fp8": ([P, P, L, P], c_int),
+        "vg_decode_attention_kv8_supported": ([I, I, I, I], c_int),
+        "vg_decode_attention_kv8": ([P, P, P, P, P, P, I, I, I, I, I, F, P, P, L, I, I, P], c_int),
         "vg_decode_qkv_rope_supported": ([I, I, I, I, I], c_int),
         "vg_decode_qkv_rope": ([P, P, L, P, F, P, P, P, P, P, I, I, I, I, I, P], c_int),
         "vg_decode_attention2_supported": ([I, I, I, I], c_int),
@@ -80,6 +83,8 @@ def _sig(lib):
         "vg_decode_step_rows_supported": ([I, I, I, I, I, I], c_int),
         "vg_decode_attention_rows_ws_floats": ([I, I, I, I, I], c_int64),
         "vg_decode_attention_rows": ([P, L, P, P, I, P, P, L, I, I, P, P, P, I, I, I, I, I, F, P, I, P, L, I, I, P], c_int),
+        "vg_decode_attention_rows_kv8_supported": ([I, I, I, I], c_int),
+        "vg_decode_attention_rows_kv8": ([P, L, P, P, I, P, P, L, I, I, P, P, P, I, I, I, I, I, F, P, I, P, L, I, I, P], c_int),
         "vg_sample_workspace_ints": ([], c_int),
         "vg_sample_partial": ([P, I, P, P, P, P, P, P, P], c_int),
         "vg_sample_partial_rows": ([P, L, I, I, P, P, P, P, P, P, P], c_int),

@@ -1241,14 +1241,49 @@ template <> __device__ __forceinline__ void st_agent_elt<bf16_t>(bf16_t* p, floa
   __hip_atomic_store(p, f2bf(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // global_store_short sc1
 }
 
+// K/V storage of the attention body.  KV = T: the cache holds the activation dtype, a lane's chunk is 16 bytes.  KV = kv8_t (bf16 activations only):
+// the cache holds OCP e4m3 codes, one byte per element and no scale, in the same [max_len, Hkv, D] layout; a chunk is still KPC = 8 elements, so
+// 8 bytes, and every (wave, chunk, lane) assignment, fmaf chain and reduction below is the bf16 body's.  e4m3 -> fp32 is exact and every e4m3
+// value is a bf16 value, so the body computes bit for bit what the bf16 body computes on the dequantised cache.
+struct kv8_t { uint8_t b; };
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+template <typename KV> struct dec_kv { typedef u32x4_t reg_t; };
+template <> struct dec_kv<kv8_t> { typedef u32x2_t reg_t; };
+template <typename KV> __device__ __forceinline__ void dec_kv_unpack(const typename dec_kv<KV>::reg_t& v, float* f) { dec_unpack<KV>(v, f); }
+template <> __device__ __forceinline__ void dec_kv_unpack<kv8_t>(const u32x2_t& v, float* f) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[e], true);
+    f[4 * e] = lo[0]; f[4 * e + 1] = lo[1]; f[4 * e + 2] = hi[0]; f[4 * e + 3] = hi[1];
+  }
+}
+// The e4m3 code of a bf16 value held in fp32: clamp to +-448 in fp32, then round to nearest even — bit for bit
+// x.float().clamp(-448, 448).to(torch.float8_e4m3fn).  A NaN keeps its sign and becomes the NaN code (0x7f / 0xff): the clamp must not eat it.
+__device__ __forceinline__ float kv8_clamp(float v) { return v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
+__device__ __forceinline__ uint32_t kv8_fix_nan(uint32_t w, float v, int byte) {
+  if (v != v) w = (w & ~(0xffu << (8 * byte))) | ((0x7fu | ((__float_as_uint(v) >> 24) & 0x80u)) << (8 * byte));
+  return w;
+}
+__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a), kv8_clamp(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(c), kv8_clamp(d), w, true);
+  uint32_t u = (uint32_t)w;
+  u = kv8_fix_nan(u, a, 0); u = kv8_fix_nan(u, b, 1); u = kv8_fix_nan(u, c, 2); u = kv8_fix_nan(u, d, 3);
+  return u;
+}
+
 // DT = compile-time head_dim (0 = run-time p.D): with it every load loop below has a constant trip count, so the
 // kernel is straight-line up to the first wait and the compiler's vmcnt bookkeeping stays exact.
 // AG (decode_layer_kernel): the merged output row leaves write-through (sc1) and *done is bumped once per KV head after it — the
 // o_proj workgroups of the same launch wait on that counter and read the row with sc1 loads.
 // LB = 64-key blocks per workgroup (2 at long caches: half as many partials to publish, arrive and merge — the merge then takes ONE pass of <= 32)
-template <typename T, int G, int DT, bool AG, int LB = 1>
+template <typename T, int G, int DT, bool AG, int LB = 1, typename KV = T>
 __device__ __forceinline__ void dec_attn_body(const DecAttnArgs& p, const int s, const int kvh, char* dec_smem, int& ticket, int* done) {
   constexpr int KPC = 16 / sizeof(T);
+  constexpr bool KV8 = std::is_same<KV, kv8_t>::value;
+  static_assert(!KV8 || sizeof(T) == 2, "the e4m3 cache goes with bf16 activations");
+  typedef typename dec_kv<KV>::reg_t kvreg_t;
   constexpr int L = 64 * LB;
   const int pos = *p.pos_dev;
   const int active = pos / L + 1;
@@ -1293,21 +1328,21 @@ __device__ __forceinline__ void dec_attn_body(const DecAttnArgs& p, const int s,
   }
   const float vn = vg_elt<T>::ld(qkv + (int64_t)(p.H + p.Hkv + kvh) * D + min(tid, D - 1));
   const int64_t rs = (int64_t)p.Hkv * D;
-  const T* kb = (const T*)p.kc + ((int64_t)j0 * p.Hkv + kvh) * D;
-  const T* vb = (const T*)p.vc + ((int64_t)j0 * p.Hkv + kvh) * D;
-  u32x4_t kreg[LB][8], vreg[LB][8];
+  const KV* kb = (const KV*)p.kc + ((int64_t)j0 * p.Hkv + kvh) * D;
+  const KV* vb = (const KV*)p.vc + ((int64_t)j0 * p.Hkv + kvh) * D;
+  kvreg_t kreg[LB][8], vreg[LB][8];
 #pragma unroll
   for (int sub = 0; sub < LB; ++sub) {
     const int jl = min(sub * 64 + lane, nk - 1);
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      if (i < NKI) kreg[sub][i] = *(const u32x4_t*)(kb + jl * rs + min(wave + 4 * i, CH - 1) * KPC);
+      if (i < NKI) kreg[sub][i] = *(const kvreg_t*)(kb + jl * rs + min(wave + 4 * i, CH - 1) * KPC);
   }
 #pragma unroll
   for (int sub = 0; sub < LB; ++sub) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      if (i < NVI) vreg[sub][i] = *(const u32x4_t*)(vb + min(sub * 64 + kslot + KP * i, nk - 1) * rs + cidx * KPC);
+      if (i < NVI) vreg[sub][i] = *(const kvreg_t*)(vb + min(sub * 64 + kslot + KP * i, nk - 1) * rs + cidx * KPC);
   }
   // ---- 2. RoPE of the G query heads and of the new key; the new value row (vg_rope_kv_append arithmetic)
 #pragma unroll
@@ -1337,11 +1372,17 @@ __device__ __forceinline__ void dec_attn_body(const DecAttnArgs& p, const int s,
   if (tid < D) vnew[tid] = vn;
   __syncthreads();
   if (s == active - 1) {   // this split holds position `pos`: append the new rows to the cache
-    T* kdst = (T*)p.kc + ((int64_t)pos * p.Hkv + kvh) * D;
-    T* vdst = (T*)p.vc + ((int64_t)pos * p.Hkv + kvh) * D;
-    if (tid < D) {
-      vg_elt<T>::st(kdst + tid, knew[tid]);
-      vg_elt<T>::st(vdst + tid, vnew[tid]);
+    KV* kdst = (KV*)p.kc + ((int64_t)pos * p.Hkv + kvh) * D;
+    KV* vdst = (KV*)p.vc + ((int64_t)pos * p.Hkv + kvh) * D;
+    if constexpr (KV8) {       // the appended row is the quantised form of the bf16 row; this step itself attends to knew / vnew unquantised (isnew below)
+      if (tid < D / 4) {
+        const int d = 4 * tid;
+        *(uint32_t*)(kdst + d) = kv8_pack4(knew[d], knew[d + 1], knew[d + 2], knew[d + 3]);
+        *(uint32_t*)(vdst + d) = kv8_pack4(vnew[d], vnew[d + 1], vnew[d + 2], vnew[d + 3]);
+      }
+    } else if (tid < D) {
+      vg_elt<T>::st((T*)kdst + tid, knew[tid]);
+      vg_elt<T>::st((T*)vdst + tid, vnew[tid]);
     }
   }
   // ---- 3. q.k: lane = key, wave w covers 16-byte chunks w, w+4, ... of the head dimension
@@ -1356,7 +1397,7 @@ __device__ __forceinline__ void dec_attn_body(const DecAttnArgs& p, const int s,
       const int c = wave + 4 * i;
       if (i < NKI && c < CH) {
         float kf[KPC];
-        dec_unpack<T>(kreg[sub][i], kf);
+        dec_kv_unpack<KV>(kreg[sub][i], kf);
         if (isnew) {
 #pragma unroll
           for (int e = 0; e < KPC; ++e) kf[e] = knew[c * KPC + e];
@@ -1409,7 +1450,7 @@ __device__ __forceinline__ void dec_attn_body(const DecAttnArgs& p, const int s,
       const int j = sub * 64 + kslot + KP * i;
       if (i < NVI && vlive && kslot + KP * i < 64 && j < nk) {      // (KP does not divide 64 at head dim 96: the last row round overshoots the block)
         float vf[KPC];
-        dec_unpack<T>(vreg[sub][i], vf);
+        dec_kv_unpack<KV>(vreg[sub][i], vf);
         if (j0 + j == pos) {
 #pragma unroll
           for (int e = 0; e < KPC; ++e) vf[e] = vnew[cidx * KPC + e];
@@ -1527,31 +1568,31 @@ __device__ __forceinline__ void dec_attn_body(const DecAttnArgs& p, const int s,
   }
 }
 
-template <typename T, int G, int DT, int LB = 1>
+template <typename T, int G, int DT, int LB = 1, typename KV = T>
 __global__ __launch_bounds__(256) void decode_attn_kernel(DecAttnArgs p) {
   extern __shared__ __attribute__((aligned(16))) char dec_smem[];
   __shared__ int ticket;
-  dec_attn_body<T, G, DT, false, LB>(p, blockIdx.x, blockIdx.y, dec_smem, ticket, nullptr);
+  dec_attn_body<T, G, DT, false, LB, KV>(p, blockIdx.x, blockIdx.y, dec_smem, ticket, nullptr);
 }
 
-template <typename T, int G, int DT, int LB = 1>
+template <typename T, int G, int DT, int LB = 1, typename KV = T>
 static void launch_decode_attn_gd(const DecAttnArgs& p, dim3 grid, size_t lds, hipStream_t st) {
   static size_t lds_cap = 64 * 1024;   // raise the dynamic-LDS cap only when a shape needs it (never inside a replay)
   if (lds > lds_cap) {
-    (void)hipFuncSetAttribute((const void*)decode_attn_kernel<T, G, DT, LB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)decode_attn_kernel<T, G, DT, LB, KV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_cap = lds;
   }
-  decode_attn_kernel<T, G, DT, LB><<<grid, 256, lds, st>>>(p);
+  decode_attn_kernel<T, G, DT, LB, KV><<<grid, 256, lds, st>>>(p);
 }
 
-template <typename T, int G>
+template <typename T, int G, typename KV = T>
 static void launch_decode_attn_g(const DecAttnArgs& p, dim3 grid, size_t lds, hipStream_t st) {
-  if (p.D == 128) launch_decode_attn_gd<T, G, 128>(p, grid, lds, st);
-  else if (p.D == 96) launch_decode_attn_gd<T, G, 96>(p, grid, lds, st);      // Phi-3-mini: the released checkpoint's LLM
-  else launch_decode_attn_gd<T, G, 0>(p, grid, lds, st);
+  if (p.D == 128) launch_decode_attn_gd<T, G, 128, 1, KV>(p, grid, lds, st);
+  else if (p.D == 96) launch_decode_attn_gd<T, G, 96, 1, KV>(p, grid, lds, st);      // Phi-3-mini: the released checkpoint's LLM
+  else launch_decode_attn_gd<T, G, 0, 1, KV>(p, grid, lds, st);
 }
 
-template <typename T>
+template <typename T, typename KV = T>
 static int launch_decode_attn(const DecAttnArgs& p, int G, int keys_per_wg, hipStream_t st) {
   constexpr int KPC = 16 / sizeof(T);
   const int KP = 256 / (p.D / KPC);
@@ -1561,17 +1602,17 @@ static int launch_decode_attn(const DecAttnArgs& p, int G, int keys_per_wg, hipS
     // 128 keys per workgroup (the caller's hint for long caches): the two shapes the pipeline decodes with — Llama-3 (G = 4, d = 128), Phi-3 (MHA, d = 96)
     if (keys_per_wg == 128 && ((G == 4 && p.D == 128) || (G == 1 && p.D == 96))) {
       lds += sizeof(float) * (4 * G * 64 + G * 64);
-      if (G == 4) launch_decode_attn_gd<T, 4, 128, 2>(p, grid, lds, st);
-      else launch_decode_attn_gd<T, 1, 96, 2>(p, grid, lds, st);
+      if (G == 4) launch_decode_attn_gd<T, 4, 128, 2, KV>(p, grid, lds, st);
+      else launch_decode_attn_gd<T, 1, 96, 2, KV>(p, grid, lds, st);
       VG_LAUNCH_CHECK();
       return VG_OK;
     }
   }
   switch (G) {
-    case 1: launch_decode_attn_g<T, 1>(p, grid, lds, st); break;
-    case 2: launch_decode_attn_g<T, 2>(p, grid, lds, st); break;
-    case 4: launch_decode_attn_g<T, 4>(p, grid, lds, st); break;
-    case 8: launch_decode_attn_g<T, 8>(p, grid, lds, st); break;
+    case 1: launch_decode_attn_g<T, 1, KV>(p, grid, lds, st); break;
+    case 2: launch_decode_attn_g<T, 2, KV>(p, grid, lds, st); break;
+    case 4: launch_decode_attn_g<T, 4, KV>(p, grid, lds, st); break;
+    case 8: launch_decode_attn_g<T, 8, KV>(p, grid, lds, st); break;
     default:
       vg_set_error("vg_decode_attention: H/Hkv = %d not in {1,2,4,8}", G);
       return VG_ERR_UNSUPPORTED;
@@ -1607,6 +1648,53 @@ extern "C" int vg_decode_attention(const void* qkv, void* k_cache, void* v_cache
   return launch_decode_attn<float>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
 }
 
+// vg_decode_attention on e4m3 caches (kv8_t above): bf16 qkv / out, the same workspace, the same shapes
+extern "C" int vg_decode_attention_kv8_supported(int H, int Hkv, int D, int dtype) {
+  if (dtype != VG_BF16 || H <= 0 || Hkv <= 0 || H % Hkv || D <= 0 || D % 8 || D > 256) return 0;
+  const int G = H / Hkv;
+  return G == 1 || G == 2 || G == 4 || G == 8;
+}
+
+extern "C" int vg_decode_attention_kv8(const void* qkv, void* k_cache, void* v_cache, const float* cos, const float* sin, void* out, int H, int Hkv,
+                                       int D, int max_len, int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats,
+                                       int keys_per_wg, int dtype, vg_stream_t stream) {
+  VG_CHECK(qkv && k_cache && v_cache && cos && sin && out && pos_dev && workspace, VG_ERR_ARG, "vg_decode_attention_kv8: null pointer");
+  VG_CHECK(keys_per_wg == 0 || keys_per_wg == 64 || keys_per_wg == 128, VG_ERR_ARG, "vg_decode_attention_kv8: keys_per_wg %d not in {0, 64, 128}",
+           keys_per_wg);
+  VG_CHECK(max_len > 0 && window >= 0, VG_ERR_ARG, "vg_decode_attention_kv8: bad max_len %d / window %d", max_len, window);
+  VG_CHECK(vg_decode_attention_kv8_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED,
+           "vg_decode_attention_kv8: H=%d Hkv=%d D=%d dtype=%d not covered (bf16, H/Hkv in {1,2,4,8}, head_dim a multiple of 8, <= 256)", H, Hkv, D, dtype);
+  VG_CHECK((((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) == 0, VG_ERR_ARG, "vg_decode_attention_kv8: caches must be 8-byte aligned");
+  const int64_t need = vg_decode_attention_ws_floats(H, Hkv, D, max_len);
+  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention_kv8: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
+  const int nsplit = (max_len + 63) / 64;
+  VG_CHECK(nsplit <= 128, VG_ERR_UNSUPPORTED, "vg_decode_attention_kv8: max_len %d > 8192", max_len);
+  DecAttnArgs p{qkv, k_cache, v_cache, cos, sin, out, workspace, (int*)(workspace + (need - Hkv)), pos_dev, H, Hkv, D, nsplit, scale, window};
+  return launch_decode_attn<bf16_t, kv8_t>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
+}
+
+// dst[i] = e4m3(src[i]) (kv8_pack4: clamp, round to nearest even, no scale) for n elements: a prefill's bf16 K / V rows -> the e4m3 cache
+__global__ __launch_bounds__(256) void kv_quantize_fp8_kernel(const bf16_t* src, uint8_t* dst, int64_t n) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i + 4 <= n) {
+    const uint32_t a = *(const uint32_t*)(src + i), b = *(const uint32_t*)(src + i + 2);
+    *(uint32_t*)(dst + i) = kv8_pack4(__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u), __uint_as_float(b << 16),
+                                      __uint_as_float(b & 0xffff0000u));
+  } else {
+    for (int64_t k = i; k < n; ++k) dst[k] = (uint8_t)(kv8_pack4(bf2f(src[k]), 0.f, 0.f, 0.f) & 0xffu);
+  }
+}
+
+extern "C" int vg_kv_quantize_fp8(const void* src, uint8_t* dst, int64_t n, vg_stream_t stream) {
+  VG_CHECK(src && dst && n > 0, VG_ERR_ARG, "vg_kv_quantize_fp8: bad args n=%lld", (long long)n);
+  VG_CHECK((((uintptr_t)src | (uintptr_t)dst) & 3) == 0, VG_ERR_ARG, "vg_kv_quantize_fp8: src and dst must be 4-byte aligned");
+  const int64_t nb = (n + 1023) / 1024;
+  VG_CHECK(nb <= 0x7fffffff, VG_ERR_UNSUPPORTED, "vg_kv_quantize_fp8: n %lld too large", (long long)n);
+  kv_quantize_fp8_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((const bf16_t*)src, dst, n);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // B query rows of vg_decode_attention at once (the batched multi-prompt decode step of the decode_attention path): grid z = row.
 // Row b is decode_attn_kernel on row b alone — its q|k|v row (qkv + b * ldqkv), RoPE at pos[b] from the shared cos / sin tables, the append of
@@ -1620,7 +1708,7 @@ struct DecAttnRowsArgs {
   void* ks; void* vs; int64_t slot_stride, ldqkv, ws_row; const int* pos; int row0, n_bound, kpw_min;
 };
 
-template <int G, int DT>
+template <int G, int DT, typename KV = bf16_t>
 __global__ __launch_bounds__(256) void decode_attn_rows_kernel(DecAttnArgs p, DecAttnRowsArgs r) {
   extern __shared__ __attribute__((aligned(16))) char dec_smem[];
   __shared__ int ticket;
@@ -1636,11 +1724,11 @@ __global__ __launch_bounds__(256) void decode_attn_rows_kernel(DecAttnArgs p, De
   q.pos_dev = r.pos + b;
   if (s * (wide ? 128 : 64) >= r.row0) {           // a per-slot split: the body's row j lands on slot row j - row0 (j >= row0 only)
     const int64_t off = b * r.slot_stride - (int64_t)r.row0 * p.Hkv * DT;
-    q.kc = (bf16_t*)r.ks + off;
-    q.vc = (bf16_t*)r.vs + off;
+    q.kc = (KV*)r.ks + off;
+    q.vc = (KV*)r.vs + off;
   }
-  if (wide) dec_attn_body<bf16_t, G, DT, false, 2>(q, s, kvh, dec_smem, ticket, nullptr);
-  else dec_attn_body<bf16_t, G, DT, false, 1>(q, s, kvh, dec_smem, ticket, nullptr);
+  if (wide) dec_attn_body<bf16_t, G, DT, false, 2, KV>(q, s, kvh, dec_smem, ticket, nullptr);
+  else dec_attn_body<bf16_t, G, DT, false, 1, KV>(q, s, kvh, dec_smem, ticket, nullptr);
 }
 
 extern "C" int vg_decode_attention_rows_supported(int H, int Hkv, int D, int dtype) {
@@ -1660,10 +1748,11 @@ extern "C" int64_t vg_decode_attention_rows_ws_floats(int H, int Hkv, int D, int
   return (int64_t)B * Hkv * nsplit * (H / Hkv) * (D + 2) + (int64_t)B * Hkv;
 }
 
-extern "C" int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots,
-                                        void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out,
-                                        int H, int Hkv, int D, int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace,
-                                        int64_t ws_floats, int B, int dtype, vg_stream_t stream) {
+// kv8: the shared caches and the slots hold e4m3 codes (vg_decode_attention_rows_kv8; slot_stride in elements = bytes)
+static int decode_attention_rows_impl(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots,
+                                      void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out,
+                                      int H, int Hkv, int D, int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace,
+                                      int64_t ws_floats, int B, int dtype, bool kv8, vg_stream_t stream) {
   VG_CHECK(qkv && k_cache && v_cache && k_slots && v_slots && cos && sin && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG,
            "vg_decode_attention_rows: bad args B=%d", B);
   VG_CHECK(vg_decode_attention_rows_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "vg_decode_attention_rows: H=%d Hkv=%d D=%d dtype=%d not covered",
@@ -1686,9 +1775,30 @@ extern "C" int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const vo
   // the LB = 2 layout (launch_decode_attn's, plus the second block's scores): LB = 1 rows use a prefix of it
   const int KP = 256 / (D / 8);
   const size_t lds = sizeof(float) * ((size_t)G * D + 2 * D + 4 * G * 64 + G * 64 + 2 * G + 4 + (size_t)KP * G * D + 4 * G * 64 + G * 64);
-  decode_attn_rows_kernel<1, 96><<<dim3(nsplit, Hkv, B), 256, lds, (hipStream_t)stream>>>(p, r);
+  if (kv8) decode_attn_rows_kernel<1, 96, kv8_t><<<dim3(nsplit, Hkv, B), 256, lds, (hipStream_t)stream>>>(p, r);
+  else decode_attn_rows_kernel<1, 96><<<dim3(nsplit, Hkv, B), 256, lds, (hipStream_t)stream>>>(p, r);
   VG_LAUNCH_CHECK();
   return VG_OK;
+}
+
+extern "C" int vg_decode_attention_rows(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots,
+                                        void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out,
+                                        int H, int Hkv, int D, int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace,
+                                        int64_t ws_floats, int B, int dtype, vg_stream_t stream) {
+  return decode_attention_rows_impl(qkv, ldqkv, k_cache, v_cache, max_len, k_slots, v_slots, slot_stride, row0, slot_rows, cos, sin, out, H, Hkv, D,
+                                    n_bound, window, scale, pos, kpw_min, workspace, ws_floats, B, dtype, false, stream);
+}
+
+extern "C" int vg_decode_attention_rows_kv8_supported(int H, int Hkv, int D, int dtype) {
+  return vg_decode_attention_rows_supported(H, Hkv, D, dtype);
+}
+
+extern "C" int vg_decode_attention_rows_kv8(const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, int max_len, void* k_slots,
+                                            void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin,
+                                            void* out, int H, int Hkv, int D, int n_bound, int window, float scale, const int* pos, int kpw_min,
+                                            float* workspace, int64_t ws_floats, int B, int dtype, vg_stream_t stream) {
+  return decode_attention_rows_impl(qkv, ldqkv, k_cache, v_cache, max_len, k_slots, v_slots, slot_stride, row0, slot_rows, cos, sin, out, H, Hkv, D,
+                                    n_bound, window, scale, pos, kpw_min, workspace, ws_floats, B, dtype, true, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

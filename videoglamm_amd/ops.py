@@ -762,17 +762,52 @@ def decode_attention_workspace(H, Hkv, D, max_len, device):
     return torch.zeros(n, dtype=torch.float32, device=device)
 
 
-def decode_attention(qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos_dev, scale, ws, window=0, keys_per_wg=0):
-    """Fused RoPE + KV append + attention of the one new token (vg_decode_attention): qkv [1,(H+2Hkv)*D] -> [1,H*D].
-    keys_per_wg=128: two 64-key blocks per workgroup (long caches: half the partials to merge)."""
+def _decode_attention(fn, qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos_dev, scale, ws, window, keys_per_wg):
     lib = _lib.load()
     assert qkv.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous() and pos_dev.dtype == torch.int32
     max_len = k_cache.shape[0]
     out = torch.empty(1, H * D, dtype=qkv.dtype, device=qkv.device)
-    rc = lib.vg_decode_attention(_p(qkv), _p(k_cache), _p(v_cache), _p(_f32(cos)), _p(_f32(sin)), _p(out), H, Hkv, D, max_len,
-                                 int(window), float(scale), _p(pos_dev), _p(ws), ws.numel(), int(keys_per_wg), _dt(qkv), _stream())
-    _lib.check(rc, "vg_decode_attention")
+    rc = getattr(lib, fn)(_p(qkv), _p(k_cache), _p(v_cache), _p(_f32(cos)), _p(_f32(sin)), _p(out), H, Hkv, D, max_len,
+                          int(window), float(scale), _p(pos_dev), _p(ws), ws.numel(), int(keys_per_wg), _dt(qkv), _stream())
+    _lib.check(rc, fn)
     return out
+
+
+def decode_attention(qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos_dev, scale, ws, window=0, keys_per_wg=0):
+    """Fused RoPE + KV append + attention of the one new token (vg_decode_attention): qkv [1,(H+2Hkv)*D] -> [1,H*D].
+    keys_per_wg=128: two 64-key blocks per workgroup (long caches: half the partials to merge)."""
+    return _decode_attention("vg_decode_attention", qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos_dev, scale, ws, window, keys_per_wg)
+
+
+# ---- fp8 K/V cache (DESIGN 8c): OCP e4m3 codes, one byte per element, no scale, the bf16 cache's [max_len, Hkv, D] layout
+def kv_quantize_reference(x):
+    """The format's definition as one torch statement (what vg_kv_quantize_fp8 and the kv8 kernels' appends reproduce bit for bit) -> uint8."""
+    return x.float().clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def kv_quantize_(src, dst):
+    """dst (uint8) <- the e4m3 codes of src (bf16), same number of elements (vg_kv_quantize_fp8); returns dst."""
+    assert src.dtype == torch.bfloat16 and dst.dtype == torch.uint8 and src.is_contiguous() and dst.is_contiguous()
+    assert src.numel() == dst.numel() and src.device == dst.device
+    if src.numel():
+        _lib.check(_lib.load().vg_kv_quantize_fp8(_p(src), _p(dst), src.numel(), _stream()), "vg_kv_quantize_fp8")
+    return dst
+
+
+def kv_dequantize(q):
+    """uint8 e4m3 codes -> bf16, exact (plain torch; tests and tools)."""
+    return q.view(torch.float8_e4m3fn).to(torch.bfloat16)
+
+
+def decode_attention_kv8_supported(H, Hkv, D, dtype):
+    return dtype == torch.bfloat16 and bool(_lib.load().vg_decode_attention_kv8_supported(H, Hkv, D, BF16))
+
+
+def decode_attention_kv8(qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos_dev, scale, ws, window=0, keys_per_wg=0):
+    """decode_attention on uint8 e4m3 caches (vg_decode_attention_kv8): bit-identical to decode_attention on kv_dequantize of them; the appended
+    row is the quantised form of the new key / value.  ws: decode_attention_workspace."""
+    assert qkv.dtype == torch.bfloat16 and k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8
+    return _decode_attention("vg_decode_attention_kv8", qkv, k_cache, v_cache, cos, sin, H, Hkv, D, pos_dev, scale, ws, window, keys_per_wg)
 
 
 def decode_rope_path(H, Hkv, D, K, dtype):
@@ -1086,16 +1121,33 @@ def decode_attention_rows(qkv, k_cache, v_cache, k_slots, v_slots, row0, cos, si
     """decode_attention on each row of qkv [B, (H+2Hkv)*D] (vg_decode_attention_rows): row b RoPE'd at pos_dev[b], its K / V rows appended into slot b
     of k_slots / v_slots ([B, rows, Hkv, D], sequence row j at j - row0), keys [0, row0) from the shared caches; 128 keys per workgroup for the rows
     at pos_dev[b] >= kpw_min -> [B, H*D]."""
+    return _decode_attention_rows("vg_decode_attention_rows", qkv, k_cache, v_cache, k_slots, v_slots, row0, cos, sin, H, Hkv, D, pos_dev, n_bound,
+                                  scale, ws, window, kpw_min)
+
+
+def decode_attention_rows_kv8_supported(H, Hkv, D, dtype):
+    return dtype == torch.bfloat16 and bool(_lib.load().vg_decode_attention_rows_kv8_supported(H, Hkv, D, BF16))
+
+
+def decode_attention_rows_kv8(qkv, k_cache, v_cache, k_slots, v_slots, row0, cos, sin, H, Hkv, D, pos_dev, n_bound, scale, ws, window=0, kpw_min=2048):
+    """decode_attention_rows with uint8 e4m3 shared caches and slots (vg_decode_attention_rows_kv8): each row bit-identical to decode_attention_kv8
+    on it alone.  ws: decode_attention_rows_workspace."""
+    assert qkv.dtype == torch.bfloat16 and all(t.dtype == torch.uint8 for t in (k_cache, v_cache, k_slots, v_slots))
+    return _decode_attention_rows("vg_decode_attention_rows_kv8", qkv, k_cache, v_cache, k_slots, v_slots, row0, cos, sin, H, Hkv, D, pos_dev,
+                                  n_bound, scale, ws, window, kpw_min)
+
+
+def _decode_attention_rows(fn, qkv, k_cache, v_cache, k_slots, v_slots, row0, cos, sin, H, Hkv, D, pos_dev, n_bound, scale, ws, window, kpw_min):
     lib = _lib.load()
     B = qkv.shape[0]
     assert qkv.stride(1) == 1 and k_cache.is_contiguous() and v_cache.is_contiguous() and k_slots.is_contiguous() and v_slots.is_contiguous()
     assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= B and k_slots.shape[0] >= B and k_slots.shape == v_slots.shape
     assert k_slots.shape[2:] == (Hkv, D) and qkv.shape[1] == (H + 2 * Hkv) * D
     out = torch.empty(B, H * D, dtype=qkv.dtype, device=qkv.device)
-    rc = lib.vg_decode_attention_rows(_p(qkv), qkv.stride(0), _p(k_cache), _p(v_cache), k_cache.shape[0], _p(k_slots), _p(v_slots), k_slots.stride(0),
-                                      int(row0), k_slots.shape[1], _p(_f32(cos)), _p(_f32(sin)), _p(out), H, Hkv, D, int(n_bound), int(window),
-                                      float(scale), _p(pos_dev), int(kpw_min), _p(ws), ws.numel(), B, _dt(qkv), _stream())
-    _lib.check(rc, "vg_decode_attention_rows")
+    rc = getattr(lib, fn)(_p(qkv), qkv.stride(0), _p(k_cache), _p(v_cache), k_cache.shape[0], _p(k_slots), _p(v_slots), k_slots.stride(0),
+                          int(row0), k_slots.shape[1], _p(_f32(cos)), _p(_f32(sin)), _p(out), H, Hkv, D, int(n_bound), int(window),
+                          float(scale), _p(pos_dev), int(kpw_min), _p(ws), ws.numel(), B, _dt(qkv), _stream())
+    _lib.check(rc, fn)
     return out
 
 

@@ -204,6 +204,44 @@ def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, suppo
     return "mfma_q"
 
 
+def kv_cache_mode(value, dtype, device_type, fused, env):
+    """cfg["llm"]["kv_cache"] -> True when the decode step keeps its keys / values as e4m3 codes, False for "bf16" (the default: the
+    cache holds the model's dtype), or ValueError saying why this decoder cannot take the mode.  dtype / device_type: the model's; fused: the fused
+    decode kernels cover the decoder (LlamaDecoder.fused_decode); env: the environment.  Pure: no device work."""
+    if value in (None, "bf16"):
+        return False
+    if value != "fp8":
+        raise ValueError(f"cfg['llm']['kv_cache'] = {value!r}: 'bf16' (default) or 'fp8'")
+    if dtype != torch.bfloat16:
+        raise ValueError(f"kv_cache = 'fp8' needs a bf16 model (the e4m3 cache holds quantised bf16 rows), not {dtype}")
+    if device_type != "cuda":
+        raise ValueError(f"kv_cache = 'fp8' runs on the GPU's decode kernels, not on device {device_type!r}")
+    if not fused:
+        raise ValueError("kv_cache = 'fp8' needs the fused decode kernels (vg_decode_attention_kv8): this decoder's shape is outside them, "
+                         "or VG_DECODE_FUSED=0")
+    if env.get("VG_DECODE_CHAIN", "0") != "0":
+        raise ValueError(f"kv_cache = 'fp8' does not combine with VG_DECODE_CHAIN={env.get('VG_DECODE_CHAIN')}: vg_decode_layer reads a bf16 cache")
+    return True
+
+
+def decode_step_form(rope_covered, attn_rows_covered, kv8=False):
+    """"rope" | "attention" | None: which B-row step (RowsDecode) goes with the decoder's single-row step.  rope_covered: the single-row step may
+    take the rope path (bf16 head_dim 128: Llama-3 width); attn_rows_covered: the B-row kernels cover the decode_attention step's layer (Phi-3-mini
+    width).  kv8 (the fp8 K/V cache): there is no rope path on e4m3 caches, so Llama-3 width runs the decode_attention form single-row and has
+    no B-row step — the mode is meant for the MHA model.  Pure."""
+    if rope_covered and not kv8:
+        return "rope"
+    return "attention" if attn_rows_covered else None
+
+
+def kv_cache_check_gemv(decode_gemv, step):
+    """ValueError when cfg["decode_gemv"] needs a step the fp8-K/V decoder no longer has: the MFMA modes run the B-row kernels in the single-row step
+    too, and at Llama-3 width those belong to the rope step.  step: decode_step_form(..., kv8=True).  Pure."""
+    if decode_gemv in ("mfma", "mfma_q") and step is None:
+        raise ValueError(f"kv_cache = 'fp8' does not combine with decode_gemv = {decode_gemv!r} on this decoder: the mode's projections belong to "
+                         "the rope step (Llama-3 width), which has no fp8 K/V form; Phi-3-mini width (the decode_attention rows step) takes both")
+
+
 class DecodeProjections:
     """Which ops entry point, which stored form of the weight and which [N, K] each projection of the LLM decode step takes — the one place where
     the modes meet.  Roles: "qkv" (the decode_attention step only: the rope step keeps q|k|v inside decode_qkv_rope), "o",
@@ -365,21 +403,31 @@ class LlamaDecoder:
         # separate launches: measured on C2 the chained launch only ties (27.4 us vs 20.1 + 8.0; 85.4 vs 84.7 for the whole layer — every
         # device-side hand-off is a fabric round trip, as the launch boundary it replaces is)
         self.chain_roles, self.chain_flags, self.chain_err = 0, None, None
-        if self.fused_decode and dev.type == "cuda":
+        # cfg["kv_cache"] == "fp8" (DESIGN 8c): the decode step reads and appends e4m3 keys / values (kc8 / vc8: one byte per element, no scale, the
+        # bf16 cache's layout); kc / vc stay as the prefill's bf16 staging — a prefill attends to unquantised K/V with today's launches, then
+        # forward() quantises the rows it wrote.  The step is the decode_attention form at every width: no rope path, no chained launch
+        self.kv8 = kv_cache_mode(c.get("kv_cache"), dt, dev.type, self.fused_decode, os.environ)
+        self.kc8 = self.vc8 = None
+        if self.kv8:
+            self.kc8 = [torch.zeros(max_len, self.Hkv, self.hd, dtype=torch.uint8, device=dev) for _ in range(c["num_layers"])]
+            self.vc8 = [torch.zeros(max_len, self.Hkv, self.hd, dtype=torch.uint8, device=dev) for _ in range(c["num_layers"])]
+        self.staged = 0      # kv8: rows [0, staged) of kc / vc are what a prefill wrote; decode steps append to kc8 / vc8 only (forward())
+        if self.fused_decode and dev.type == "cuda" and not self.kv8:
             self.chain_roles = min(ops.decode_layer_roles(self.H, self.Hkv, self.hd, self.D, ffn, dt), int(os.environ.get("VG_DECODE_CHAIN", "0")))
             if self.chain_roles == 2:
                 self.chain_roles = 1
         # r06: RoPE + KV append in the q|k|v GEMV's epilogue, attention as a wave-private flash pass (bf16, head_dim 128); VG_DECODE_ROPE=0 = A/B knob
-        self.rope_path = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
-                          and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
+        rope_covered = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
+                        and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
+        rows_covered = (self.fused_decode and dev.type == "cuda" and not self.chain_roles
+                        and ops.decode_step_rows_supported(self.H, self.Hkv, self.hd, self.D, ffn, dt))
+        step = decode_step_form(rope_covered, rows_covered, self.kv8)
+        self.rope_path = step == "rope"
         self.kpw2 = int(os.environ.get("VG_DEC2_KPW", "256"))
         # cfg["decode_gemv"] ("valu" | "mfma" | "mfma_q") x cfg["decode_weights"]: which kernel and stored weight each projection of the single-row
         # and the B-row step takes is DecodeProjections' answer; decode_gemv_mode refuses what this decoder cannot run before any launch
-        step = None
-        if self.rope_path:
-            step = "rope"
-        elif self.fused_decode and dev.type == "cuda" and not self.chain_roles and ops.decode_step_rows_supported(self.H, self.Hkv, self.hd, self.D, ffn, dt):
-            step = "attention"
+        if self.kv8:
+            kv_cache_check_gemv(c.get("decode_gemv"), step)
         head = params.sd.get("lm_head.weight")       # (a decoder that only prefills may come without one)
         self.proj = DecodeProjections(c.get("decode_gemv"), c.get("decode_weights"), hidden=self.D, ffn=ffn, vocab=0 if head is None else head.shape[0],
                                       qkv=(self.H + 2 * self.Hkv) * self.hd, attn=self.H * self.hd, step=step, pack=dt == torch.bfloat16)
@@ -494,8 +542,9 @@ class LlamaDecoder:
                     if mlp is not None:
                         continue
                 else:
-                    o = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd,
-                                             self.pos_dev, self.hd ** -0.5, self.attn_ws, window=self.window, keys_per_wg=self.kpw)
+                    attn, kc, vc = (ops.decode_attention_kv8, self.kc8, self.vc8) if self.kv8 else (ops.decode_attention, self.kc, self.vc)
+                    o = attn(qkv, kc[i], vc[i], self.cos, self.sin, self.H, self.Hkv, self.hd,
+                             self.pos_dev, self.hd ** -0.5, self.attn_ws, window=self.window, keys_per_wg=self.kpw)
                     x = pr.run("o", False, P, l, o, residual=x)
             # the MLP (81 % of a layer's bytes) in the decode weights' format — the attention projections stay bf16: at K = 4096 an fp8 row is
             # a single batch of loads per lane and the per-row reduction eats the gain (10.4 vs 9.1 us measured)
@@ -506,7 +555,17 @@ class LlamaDecoder:
         """eager: x [S,D] new tokens appended at self.pos -> final-normed hidden [S,D] (also kept in hid_all)."""
         S, pos = x.shape[0], self.pos
         assert pos + S <= self.max_len
+        if self.kv8 and pos > self.staged:
+            # rows [staged, pos) came from decode steps, which append to the e4m3 cache only: the staging takes what that cache holds
+            for i in range(self.c["num_layers"]):
+                self.kc[i][self.staged:pos].copy_(ops.kv_dequantize(self.kc8[i][self.staged:pos]))
+                self.vc[i][self.staged:pos].copy_(ops.kv_dequantize(self.vc8[i][self.staged:pos]))
         h = self._layers(x, pos, None)
+        if self.kv8:
+            for i in range(self.c["num_layers"]):      # the rows this prefill wrote, [pos, pos + S), into the cache the decode step reads
+                ops.kv_quantize_(self.kc[i][pos:pos + S], self.kc8[i][pos:pos + S])
+                ops.kv_quantize_(self.vc[i][pos:pos + S], self.vc8[i][pos:pos + S])
+            self.staged = pos + S
         self.hid_all[pos:pos + S].copy_(h)
         self.pos = pos + S
         self.pos_dev.fill_(self.pos)
@@ -520,6 +579,8 @@ class LlamaDecoder:
         prefill costs 1/world per rank (plus one weight pass) instead of a whole one on every rank; the final-norm rows are
         all-gathered at the end (the replicated decode continues from the last one)."""
         c = self.c
+        if self.kv8:
+            raise ValueError("kv_cache = 'fp8' has no sequence-parallel prefill (forward_sharded): run the model on one GPU, or keep kv_cache = 'bf16'")
         S, W, r = x.shape[0], comm.world, comm.rank
         m = -(-S // W)
         a = min(r * m, S)
@@ -601,6 +662,8 @@ class LlamaDecoder:
         # long caches: two 64-key blocks per decode-attention workgroup (half the partials to publish, arrive and merge: the merge of a C2 prompt's
         # 54 splits took two passes); a launch parameter, so each setting has its own captured graph.  VG_DEC_KPW_MIN = first position that uses it
         self.kpw = 128 if (self.pos >= self.kpw_min and not self.rope_path) else 0
+        if self.kv8:
+            self.staged = min(self.staged, self.pos)       # row pos is appended to the e4m3 cache only
         # the route (greedy / fast / general sampler) is part of the captured launches; T, k, p and the seed are not
         key = self.kpw if self.sampling is None else (self.kpw, "sample_fast" if self.samp_fast else "sample")
         self.graph = self.graphs.get(key)
@@ -654,8 +717,11 @@ class RowsDecode:
         self.attn_rows = not d.rope_path
         assert row0 % (self.ATTN_KW if self.attn_rows else d.kpw2) == 0
         rows = n_bound - row0
-        self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
-        self.vs = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=dt, device=dev) for _ in range(d.c["num_layers"])]
+        self.kv8 = bool(getattr(d, "kv8", False))       # the decoder's fp8 K/V cache: the slots hold e4m3 codes as kc8 / vc8 do
+        assert self.attn_rows or not self.kv8
+        kdt = torch.uint8 if self.kv8 else dt
+        self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=kdt, device=dev) for _ in range(d.c["num_layers"])]
+        self.vs = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=kdt, device=dev) for _ in range(d.c["num_layers"])]
         self.hid = torch.zeros(B, rows, d.D, dtype=dt, device=dev)
         self.tok = torch.zeros(B, dtype=torch.int64, device=dev)
         self.pos = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -681,9 +747,10 @@ class RowsDecode:
         """row b continues from the decoder's state after prompt b's suffix prefill and first token: its K / V rows [row0, end) and final-norm rows
         [P, end) are copied into slot b; token, position (end), step (1: the prefill's token is step 0) and sampling block from the decoder."""
         d = self.dec
+        kc, vc = (d.kc8, d.vc8) if self.kv8 else (d.kc, d.vc)
         for i in range(d.c["num_layers"]):
-            self.ks[i][b, :end - self.row0].copy_(d.kc[i][self.row0:end])
-            self.vs[i][b, :end - self.row0].copy_(d.vc[i][self.row0:end])
+            self.ks[i][b, :end - self.row0].copy_(kc[i][self.row0:end])
+            self.vs[i][b, :end - self.row0].copy_(vc[i][self.row0:end])
         self.hid[b, P - self.row0:end - self.row0].copy_(d.hid_all[P:end])
         self.host_pos[b] = self.start_pos[b] = end
         self.tok[b:b + 1].copy_(d.tok_dev)
@@ -712,8 +779,9 @@ class RowsDecode:
             l = f"model.layers.{i}."
             if self.attn_rows:
                 qkv = pr.run("qkv", True, P, l, x, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
-                o = ops.decode_attention_rows(qkv, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.cos, d.sin, d.H, d.Hkv, d.hd, self.pos,
-                                              self.n_bound, d.hd ** -0.5, self.attn_ws, window=d.window, kpw_min=d.kpw_min)
+                attn, kc, vc = (ops.decode_attention_rows_kv8, d.kc8, d.vc8) if self.kv8 else (ops.decode_attention_rows, d.kc, d.vc)
+                o = attn(qkv, kc[i], vc[i], self.ks[i], self.vs[i], self.row0, d.cos, d.sin, d.H, d.Hkv, d.hd, self.pos,
+                         self.n_bound, d.hd ** -0.5, self.attn_ws, window=d.window, kpw_min=d.kpw_min)
             else:
                 q = ops.decode_qkv_rope_rows(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i],
                                              self.row0, self.rope_cs, self.pos, d.H, d.Hkv, d.hd)

@@ -341,6 +341,32 @@ int vg_decode_attention_rows_kv8(const void* qkv, int64_t ldqkv, const void* k_c
                                  int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out, int H, int Hkv, int D,
                                  int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace, int64_t ws_floats, int B,
                                  int dtype, vg_stream_t stream);
+/* The fp8 K/V format above on the rope step (cfg kv_cache = "fp8_rope"): bf16 activations, uint8 e4m3 caches and slots in
+ *   the [rows, Hkv, D] layout, 8-byte aligned; slot_stride in elements (= bytes), a multiple of 8.  Everything not named here is the bf16 entry
+ *   point's: arguments, shapes, workspaces (vg_decode_attention_ws_floats / vg_decode_attention2_rows_ws_floats), premises.
+ * vg_decode_qkv_rope_kv8 / _rows_kv8: vg_decode_qkv_rope / _rows with byte K/V destinations.  q_out is bit-identical; the key / value row written
+ *   at *pos_dev (slot row pos[b] - row0, clamped) holds the codes of the bf16 row the bf16 entry point writes (quantised after its bf16 rounding:
+ *   clamp, nearest even, NaN kept); no other byte of the caches is touched.  bf16 only, K in {2048, 4096}; fp32 is VG_ERR_UNSUPPORTED.
+ * vg_decode_attention2_kv8 / _rows_kv8: vg_decode_attention2 / _rows on such caches.  The codes are converted exactly (K to packed bf16, V to fp32)
+ *   and every sum runs in the bf16 kernel's order, so the output is bit-identical to the bf16 entry point on the dequantised caches and slots.
+ *   Every row finite (a zero byte is +0.0: zero-filled caches satisfy it); rows past the position are masked, not skipped.
+ *   vg_decode_attention2_kv8_supported = vg_decode_attention2_supported (bf16, D = 128, H / Hkv in {1, 2, 4, 8}); keys_per_wg 128 / 256.
+ * Unlike vg_decode_attention_kv8, where the new token's key / value take part in their own step unquantised, here they are in the cache before the
+ *   attention launch reads it: the new token attends to its own key / value already quantised. */
+int vg_decode_qkv_rope_kv8(const void* x, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, uint8_t* k_cache,
+                           uint8_t* v_cache, const float* rope_cs, const int* pos_dev, int H, int Hkv, int D, int K, int dtype,
+                           vg_stream_t stream);
+int vg_decode_qkv_rope_rows_kv8(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, int64_t ldq,
+                                uint8_t* k_slots, uint8_t* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* rope_cs,
+                                const int* pos, int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream);
+int vg_decode_attention2_kv8_supported(int H, int Hkv, int D, int dtype);
+int vg_decode_attention2_kv8(const void* q, const uint8_t* k_cache, const uint8_t* v_cache, void* out, int H, int Hkv, int D, int max_len,
+                             int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg, int dtype,
+                             vg_stream_t stream);
+int vg_decode_attention2_rows_kv8(const void* q, const uint8_t* k_cache, const uint8_t* v_cache, int max_len, const uint8_t* k_slots,
+                                  const uint8_t* v_slots, int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D, int n_bound,
+                                  int window, float scale, const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg, int B, int dtype,
+                                  vg_stream_t stream);
 /* Sampled decoding (csrc/vg_sample.hip): HF's Temperature -> TopK -> TopP warpers and the draw on one fp32 logits row x[n]
  *   (n < 2^22), one launch.  params: the 24-byte device block {float T; float p; int k; int pad; uint64 seed} (k = 0: no top-k; p = 1: no top-p).
  * vg_sample_partial — acc[0] = the drawn entry's packed (ordered value bits, ~index) key, the hand-off vg_argmax_partial leaves, so

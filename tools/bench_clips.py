@@ -15,13 +15,13 @@ the modes alternate inside each repetition (loop, clips and the replayed step of
 --decode-weights bf16 fp8 mxfp4: cfg["llm"]["decode_weights"]; every valid (decode_gemv, decode_weights) pair is one model and one line
 ("decode_weights" in the record), all alternating inside each repetition; an invalid pair (mfma with fp8 / mxfp4, mfma_q with bf16) is skipped
 with a printed line.
---kv-cache bf16 fp8: cfg["llm"]["kv_cache"]; each value is one more model per pair ("kv_cache" in the record), alternating with the
+--kv-cache bf16 fp8 fp8_rope: cfg["llm"]["kv_cache"] (fp8_rope at Llama-3 width only); each value is one more model per pair ("kv_cache" in the record), alternating with the
 others inside each repetition.  "slot_bytes"[B]: the bytes of the batched state's K / V slots (RowsDecode.ks + vs) behind that B.
 --out FILE also appends the lines to FILE (the raw record behind DESIGN 12's table lives in profiles/).
 
     python tools/bench_clips.py [--llm llama3-8b phi3-mini] [--batches 1 2 4 8 16] [--reps 3] [--warmup 1] [--branch framewise]
                                  [--sample k50 k0] [--decode-gemv valu mfma mfma_q] [--decode-weights bf16 fp8 mxfp4]
-                                 [--kv-cache bf16 fp8] [--out FILE]
+                                 [--kv-cache bf16 fp8 fp8_rope] [--out FILE]
 """
 import argparse
 import json
@@ -145,7 +145,7 @@ def main():
                     help="cfg['llm']['decode_gemv']; several: the modes alternate inside each repetition, one line per mode")
     ap.add_argument("--decode-weights", nargs="+", default=["bf16"], choices=["bf16", "fp8", "mxfp4"],
                     help="cfg['llm']['decode_weights']; every valid pair with --decode-gemv is one model, invalid pairs are skipped")
-    ap.add_argument("--kv-cache", nargs="+", default=["bf16"], choices=["bf16", "fp8"],
+    ap.add_argument("--kv-cache", nargs="+", default=["bf16"], choices=["bf16", "fp8", "fp8_rope"],
                     help="cfg['llm']['kv_cache']; each value is one more model per (decode_gemv, decode_weights) pair")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()

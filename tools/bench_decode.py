@@ -1,12 +1,12 @@
 """Decode-loop microbenchmark: Llama-3-8B (synthetic weights), prefill of S random embeddings, then G graph-replayed
 decode steps; the 16 GB of weights stream from HBM every token (no MALL flattery as in a single-matrix loop).
-usage: python tools/bench_decode.py [S=1697] [G=32] [decode_weights=bf16,fp8,mxfp4] [kv_cache=bf16,fp8] [llm=llama3-8b|phi3-mini] [reps=3] [out=FILE]
+usage: python tools/bench_decode.py [S=1697] [G=32] [decode_weights=bf16,fp8,mxfp4] [kv_cache=bf16,fp8,fp8_rope] [llm=llama3-8b|phi3-mini] [reps=3] [out=FILE]
 env: VG_DECODE_FUSED=0/1
 decode_weights=...: one decoder per mode (cfg["llm"]["decode_weights"]) on the fused kernels, all built, prefilled and captured first; then `reps`
 repetitions of G replayed steps per mode, the modes alternating inside every repetition and each repetition starting again at position S.  Per mode:
 ms per token of every repetition, their median and spread (max - min).  out=FILE appends the printed lines to FILE.
 kv_cache=...: cfg["llm"]["kv_cache"]; with it (and / or decode_weights=) every (decode_weights, kv_cache) pair is one decoder, all alternating;
-under kv_cache=fp8 the single-row step is the decode_attention form at either width.  llm=phi3-mini: the released checkpoint's LLM (MHA, head_dim 96)."""
+under kv_cache=fp8 the single-row step is the decode_attention form at either width; kv_cache=fp8_rope is the rope step on e4m3 caches (Llama-3 width only).  llm=phi3-mini: the released checkpoint's LLM (MHA, head_dim 96)."""
 import os
 import statistics
 import sys

@@ -1,9 +1,10 @@
 """Masks of the fp8 LLM path (fp8 MFMA prefill + fp8 decode weights) against the bf16 path on the full-size synthetic C1
 model (Llama-3-8B + towers + SAM2-L, random weights), teacher-forced: the fp8 run is made to emit the ids of the bf16 run, so
 the [SEG] hidden states differ by the fp8 arithmetic only.  Prints the cosine of the [SEG] embeddings seen by SAM2 (through the
-masks) and the per-mask IoU.  usage: python tools/fp8_mask_iou.py [objects] [--kv-cache fp8] [--llm llama3-8b|phi3-mini]
+masks) and the per-mask IoU.  usage: python tools/fp8_mask_iou.py [objects] [--kv-cache fp8|fp8_rope] [--llm llama3-8b|phi3-mini]
 --kv-cache fp8: the run compared against bf16 is instead the fp8 K/V cache (cfg["llm"]["kv_cache"] = "fp8"; bf16 weights), teacher-forced
-the same way; also printed per step: the relative error and the cosine of the lm_head logits against the bf16 run's, and the argmax agreement.
+the same way (--kv-cache fp8_rope: the same format on the rope step, Llama-3 width only; the new token there attends to its own K/V quantised);
+also printed per step: the relative error and the cosine of the lm_head logits against the bf16 run's, and the argmax agreement.
 --llm phi3-mini: the released checkpoint's LLM (MHA, head_dim 96: the model the K/V mode is meant for)."""
 import argparse
 import os
@@ -19,7 +20,7 @@ from videoglamm_amd.model import VideoGLaMMForCausalLM  # noqa: E402
 torch.set_grad_enabled(False)
 ap = argparse.ArgumentParser()
 ap.add_argument("objects", type=int, nargs="?", default=3)
-ap.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8"])
+ap.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8", "fp8_rope"])
 ap.add_argument("--llm", default="llama3-8b", choices=["llama3-8b", "phi3-mini"])
 args = ap.parse_args()
 objects = args.objects
@@ -49,8 +50,8 @@ def step_logits(m):
 ref_logits = step_logits(base)
 del base
 runs = (("fp8 decode weights", dict(cfg["llm"], decode_weights="fp8")), ("fp8 prefill + decode weights", dict(cfg["llm"], decode_weights="fp8", prefill_gemm="fp8")))
-if args.kv_cache == "fp8":
-    runs = (("fp8 K/V cache", dict(cfg["llm"], kv_cache="fp8")),)
+if args.kv_cache != "bf16":
+    runs = ((f"fp8 K/V cache ({args.kv_cache})", dict(cfg["llm"], kv_cache=args.kv_cache)),)
 for name, llm in runs:
     sd["_"] = None
     sd.pop("_")
@@ -64,7 +65,7 @@ for name, llm in runs:
     flat = np.array(iou).ravel()
     print(f"{name}: {ref.shape[1]} objects x {T} frames, mask IoU vs bf16: mean {flat.mean():.4f} median {np.median(flat):.4f} min {flat.min():.4f}")
     print("   per-mask [t][n]:", np.round(np.array(iou), 3).tolist())
-    if args.kv_cache == "fp8":
+    if args.kv_cache != "bf16":
         lg = step_logits(m)
         rel = ((lg - ref_logits).norm(dim=1) / ref_logits.norm(dim=1)).tolist()
         cos = torch.nn.functional.cosine_similarity(lg, ref_logits, dim=1).tolist()

@@ -1,7 +1,7 @@
 """The replayed batched decode step under rocprofv3 --kernel-trace --stats, and the per-kernel table of its dispatches.
 
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/rows_step_trace.py run [--llm llama3-8b] [--batch 16] [--decode-gemv mfma | mfma_q]
-                                                                            [--decode-weights fp8 | mxfp4] [--kv-cache fp8]
+                                                                            [--decode-weights fp8 | mxfp4] [--kv-cache fp8 | fp8_rope]
     python tools/rows_step_trace.py table DIR/kt_results.db [--steps 24] > profiles/NAME.txt
 
 run:   clips.generate_clips with --batch clips (a visual block of 1694 rows each, questions of 30..45 ids, 4 new tokens) at the LLM's full depth
@@ -100,7 +100,7 @@ def main():
     r.add_argument("--batch", type=int, default=16)
     r.add_argument("--decode-gemv", default="valu", choices=["valu", "mfma", "mfma_q"])
     r.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"], help="mfma_q pairs with fp8 / mxfp4, mfma with bf16")
-    r.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8"], help="cfg['llm']['kv_cache'] (DESIGN 8c)")
+    r.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8", "fp8_rope"], help="cfg['llm']['kv_cache'] (DESIGN 8c)")
     r.add_argument("--steps", type=int, default=24)
     t = sub.add_parser("table")
     t.add_argument("db")

@@ -85,6 +85,11 @@ def _sig(lib):
         "vg_decode_attention_rows": ([P, L, P, P, I, P, P, L, I, I, P, P, P, I, I, I, I, I, F, P, I, P, L, I, I, P], c_int),
         "vg_decode_attention_rows_kv8_supported": ([I, I, I, I], c_int),
         "vg_decode_attention_rows_kv8": ([P, L, P, P, I, P, P, L, I, I, P, P, P, I, I, I, I, I, F, P, I, P, L, I, I, P], c_int),
+        "vg_decode_qkv_rope_kv8": ([P, P, L, P, F, P, P, P, P, P, I, I, I, I, I, P], c_int),
+        "vg_decode_qkv_rope_rows_kv8": ([P, L, P, L, P, F, P, L, P, P, L, I, I, P, P, I, I, I, I, I, I, P], c_int),
+        "vg_decode_attention2_kv8_supported": ([I, I, I, I], c_int),
+        "vg_decode_attention2_kv8": ([P, P, P, P, I, I, I, I, I, F, P, P, L, I, I, P], c_int),
+        "vg_decode_attention2_rows_kv8": ([P, P, P, I, P, P, L, I, I, P, I, I, I, I, I, F, P, P, L, I, I, I, P], c_int),
         "vg_sample_workspace_ints": ([], c_int),
         "vg_sample_partial": ([P, I, P, P, P, P, P, P, P], c_int),
         "vg_sample_partial_rows": ([P, L, I, I, P, P, P, P, P, P, P], c_int),

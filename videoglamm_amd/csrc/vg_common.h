@@ -11,6 +11,19 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+// an element of an fp8 K/V cache: an OCP e4m3 code, one byte, no scale.  The K/V storage parameter of the decode attention kernels
+// (vg_decode.hip: dec_attn_body; vg_decode2.hip: decode_attn2_kernel) and of the rope projections' epilogues
+struct kv8_t { uint8_t b; };
+// a lane's 8-element chunk of such a cache -> fp32, exact
+__device__ __forceinline__ void kv8_unpack8(const u32x2_t& v, float* f) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[e], true);
+    f[4 * e] = lo[0]; f[4 * e + 1] = lo[1]; f[4 * e + 2] = hi[0]; f[4 * e + 3] = hi[1];
+  }
+}
 
 #define VG_WAVE 64
 

@@ -114,6 +114,29 @@ struct DecGemvArgs {
 // weight 8 u + j = element j of chunk (batch * 256 + u * 64 + lane).
 constexpr int DEC_P13_BLOCK = 3328;
 
+// The e4m3 code of a bf16 value held in fp32 (the fp8 K/V cache): clamp to +-448 in fp32, then round to nearest even — bit for bit
+// x.float().clamp(-448, 448).to(torch.float8_e4m3fn).  A NaN keeps its sign and becomes the NaN code (0x7f / 0xff): the clamp must not eat it.
+__device__ __forceinline__ float kv8_clamp(float v) { return v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
+__device__ __forceinline__ uint32_t kv8_fix_nan(uint32_t w, float v, int byte) {
+  if (v != v) w = (w & ~(0xffu << (8 * byte))) | ((0x7fu | ((__float_as_uint(v) >> 24) & 0x80u)) << (8 * byte));
+  return w;
+}
+__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a), kv8_clamp(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(c), kv8_clamp(d), w, true);
+  uint32_t u = (uint32_t)w;
+  u = kv8_fix_nan(u, a, 0); u = kv8_fix_nan(u, b, 1); u = kv8_fix_nan(u, c, 2); u = kv8_fix_nan(u, d, 3);
+  return u;
+}
+// The rope epilogues' store of a rotate-half pair (d, d + RHD) of a key / value head into an e4m3 cache (KVO = kv8_t below; KVO = the activation
+// type is the plain store): two byte stores of the codes of the bf16 values the bf16 cache would have held — the values are rounded to bf16
+// first, as that cache's store rounds them — and no other byte of the row is read or written.
+__device__ __forceinline__ void kv8_store_pair(kv8_t* dst, int hi, float o1, float o2) {
+  const uint32_t w = kv8_pack4(bf2f(f2bf(o1)), bf2f(f2bf(o2)), 0.f, 0.f);
+  dst[0].b = (uint8_t)(w & 0xffu);
+  dst[hi].b = (uint8_t)((w >> 8) & 0xffu);
+}
+
 template <typename T, typename TO, bool GLU>
 __device__ __forceinline__ void dec_gemv_store(const DecGemvArgs& p, int pi, float a0, float a1) {
   const int n0 = GLU ? pi : 2 * pi, n1 = GLU ? p.N + pi : 2 * pi + 1;
@@ -165,7 +188,7 @@ constexpr int DEC_MAX_PPW = 64;
 //   * the multiplication by 2^-k (p.wscale, a normal fp32 power of two) after wave_sum is exact under the same condition.
 // The condition is a premise on the data (|x| within 2^+-60 is ample); a raw row does not lean on it: it is recomputed (3b below)
 // from the bf16 matrix with the bf16 kernel's own code, and its wscale is 1.
-template <typename T, typename TO, bool GLU, int NB, int CPB = 4, bool W8 = false, int RHD = 0, bool P13 = false>
+template <typename T, typename TO, bool GLU, int NB, int CPB = 4, bool W8 = false, int RHD = 0, bool P13 = false, typename KVO = TO>
 __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
   extern __shared__ __attribute__((aligned(16))) char dec_smem[];
   __shared__ float red[4];
@@ -350,6 +373,7 @@ __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
   }
   // ---- 4. epilogue: one lane per pair
   if constexpr (RHD > 0) {
+    constexpr bool KV8O = std::is_same<KVO, kv8_t>::value;      // byte K/V destinations (vg_decode_qkv_rope_kv8)
     const int pos = *p.pos_dev;
     for (int i = lane; i < np; i += 64) {
       const int pi = p0 + i, hh = pi / RHD, d = pi % RHD;
@@ -366,8 +390,12 @@ __global__ __launch_bounds__(256) void decode_gemv_fast_kernel(DecGemvArgs p) {
           o1 = x1 * c - x2 * sv;
           o2 = x2 * c + x1 * sv;
         }
+        if constexpr (KV8O) {
+          if (hh >= p.H) { kv8_store_pair((KVO*)p.kc + ((int64_t)pos * p.Hkv + (hh - p.H)) * (2 * RHD) + d, RHD, o1, o2); continue; }
+        }
         dst = hh < p.H ? (TO*)p.y + (int64_t)hh * (2 * RHD) : (TO*)p.kc + ((int64_t)pos * p.Hkv + (hh - p.H)) * (2 * RHD);
       } else {
+        if constexpr (KV8O) { kv8_store_pair((KVO*)p.vc + ((int64_t)pos * p.Hkv + (hh - p.H - p.Hkv)) * (2 * RHD) + d, RHD, o1, o2); continue; }
         dst = (TO*)p.vc + ((int64_t)pos * p.Hkv + (hh - p.H - p.Hkv)) * (2 * RHD);
       }
       vg_elt<TO>::st(dst + d, o1);
@@ -714,7 +742,7 @@ extern "C" int vg_decode_qkv_rope_supported(int H, int Hkv, int D, int K, int dt
   return 0;
 }
 
-template <typename T, int NB>
+template <typename T, int NB, typename KVO = T>
 static int launch_decode_qkv_rope(DecGemvArgs p, hipStream_t st) {
   const int npair = p.N / 2;
   const int maxw = 256 * 2 * 4;
@@ -724,7 +752,7 @@ static int launch_decode_qkv_rope(DecGemvArgs p, hipStream_t st) {
   if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
   p.ppw = ppw;
   const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
-  decode_gemv_fast_kernel<T, T, false, NB, 4, false, 64><<<blocks, 256, (size_t)p.K * sizeof(T), st>>>(p);
+  decode_gemv_fast_kernel<T, T, false, NB, 4, false, 64, false, KVO><<<blocks, 256, (size_t)p.K * sizeof(T), st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
@@ -742,6 +770,21 @@ extern "C" int vg_decode_qkv_rope(const void* x, const void* Wqkv, int64_t ldw, 
   hipStream_t st = (hipStream_t)stream;
   if (dtype == VG_BF16) return K == 4096 ? launch_decode_qkv_rope<bf16_t, 2>(p, st) : launch_decode_qkv_rope<bf16_t, 1>(p, st);
   return launch_decode_qkv_rope<float, 4>(p, st);
+}
+
+// vg_decode_qkv_rope with e4m3 K/V destinations (kv_cache = "fp8_rope"): the same kernel, the key / value pairs stored by
+// kv8_store_pair; q_out has the bf16 entry point's bits
+extern "C" int vg_decode_qkv_rope_kv8(const void* x, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, uint8_t* k_cache,
+                                      uint8_t* v_cache, const float* rope_cs, const int* pos_dev, int H, int Hkv, int D, int K, int dtype,
+                                      vg_stream_t stream) {
+  VG_CHECK(x && Wqkv && q_out && k_cache && v_cache && rope_cs && pos_dev, VG_ERR_ARG, "vg_decode_qkv_rope_kv8: null pointer");
+  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
+           "vg_decode_qkv_rope_kv8: H=%d Hkv=%d D=%d K=%d dtype=%d not covered (bf16 only)", H, Hkv, D, K, dtype);
+  VG_CHECK(ldw % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)Wqkv & 15) == 0 && ((uintptr_t)norm_w & 15) == 0, VG_ERR_ARG,
+           "vg_decode_qkv_rope_kv8: alignment (16 bytes; ldw a multiple of 8)");
+  DecGemvArgs p{x, Wqkv, q_out, norm_w, nullptr, (H + 2 * Hkv) * D, K, ldw, eps, 1, nullptr, rope_cs, pos_dev, k_cache, v_cache, H, Hkv};
+  hipStream_t st = (hipStream_t)stream;
+  return K == 4096 ? launch_decode_qkv_rope<bf16_t, 2, kv8_t>(p, st) : launch_decode_qkv_rope<bf16_t, 1, kv8_t>(p, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -764,7 +807,7 @@ struct DecRowsArgs {
 
 template <int NB> constexpr int dec_rows_cpb() { return NB == 3 ? 2 : 4; }     // chunks per lane per batch: 2 only at K = 3072
 
-template <typename TO, bool GLU, int NB, int BR, int RHD>
+template <typename TO, bool GLU, int NB, int BR, int RHD, typename KVO = TO>
 __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
   typedef bf16_t T;
   constexpr int CPB = dec_rows_cpb<NB>(), KPC = 8, NWV = 2;
@@ -882,6 +925,7 @@ __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
     const int li = i / BR, r = i % BR, pi = p0 + li;
     if (r >= p.B) continue;
     if constexpr (RHD > 0) {
+      constexpr bool KV8O = std::is_same<KVO, kv8_t>::value;      // byte K/V slots (vg_decode_qkv_rope_rows_kv8)
       const int pos = p.pos[r];
       const int srow = min(max(pos - p.row0, 0), p.slot_rows - 1);    // a slot's rows only, whatever the position word holds
       const int hh = pi / RHD, d = pi % RHD;
@@ -893,9 +937,19 @@ __global__ __launch_bounds__(256) void decode_gemv_rows_kernel(DecRowsArgs p) {
         const float cb = bf2f(f2bf(c)), sb = bf2f(f2bf(sv));
         o1 = bf2f(f2bf(x1 * cb)) + bf2f(f2bf(-x2 * sb));
         o2 = bf2f(f2bf(x2 * cb)) + bf2f(f2bf(x1 * sb));
+        if constexpr (KV8O) {
+          if (hh >= p.H) {
+            kv8_store_pair((KVO*)p.kc + r * p.slot_stride + ((int64_t)srow * p.Hkv + (hh - p.H)) * (2 * RHD) + d, RHD, o1, o2);
+            continue;
+          }
+        }
         dst = hh < p.H ? (TO*)p.y + r * p.ldy + (int64_t)hh * (2 * RHD)
                        : (TO*)p.kc + r * p.slot_stride + ((int64_t)srow * p.Hkv + (hh - p.H)) * (2 * RHD);
       } else {
+        if constexpr (KV8O) {
+          kv8_store_pair((KVO*)p.vc + r * p.slot_stride + ((int64_t)srow * p.Hkv + (hh - p.H - p.Hkv)) * (2 * RHD) + d, RHD, o1, o2);
+          continue;
+        }
         dst = (TO*)p.vc + r * p.slot_stride + ((int64_t)srow * p.Hkv + (hh - p.H - p.Hkv)) * (2 * RHD);
       }
       vg_elt<TO>::st(dst + d, o1);
@@ -926,7 +980,7 @@ extern "C" int vg_decode_rows_supported(int H, int Hkv, int D, int hidden, int i
   return dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, hidden, dtype) && dec_rows_nb4(hidden) && dec_rows_nb4(inter) && (H * D) == hidden;
 }
 
-template <typename TO, bool GLU, int NB, int BR, int RHD>
+template <typename TO, bool GLU, int NB, int BR, int RHD, typename KVO = TO>
 static int launch_rows_b(DecRowsArgs p, hipStream_t st) {
   const int npair = RHD > 0 ? p.N / 2 : GLU ? p.N : (p.N + 1) / 2;
   constexpr int BBYTES = dec_rows_cpb<NB>() * 64 * 16;     // bytes of one row's batch of chunks
@@ -940,21 +994,21 @@ static int launch_rows_b(DecRowsArgs p, hipStream_t st) {
   const size_t lds = (size_t)BR * nph * BBYTES;
   static size_t cap = 64 * 1024;
   if (lds > 64 * 1024 && lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD, KVO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     cap = lds;
   }
-  decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
+  decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD, KVO><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
 
-template <typename TO, bool GLU, int NB, int RHD>
+template <typename TO, bool GLU, int NB, int RHD, typename KVO = TO>
 static int launch_rows_nb(DecRowsArgs p, hipStream_t st) {
-  if (p.B <= 1) return launch_rows_b<TO, GLU, NB, 1, RHD>(p, st);
-  if (p.B <= 2) return launch_rows_b<TO, GLU, NB, 2, RHD>(p, st);
-  if (p.B <= 4) return launch_rows_b<TO, GLU, NB, 4, RHD>(p, st);
-  if (p.B <= 8) return launch_rows_b<TO, GLU, NB, 8, RHD>(p, st);
-  return launch_rows_b<TO, GLU, NB, 16, RHD>(p, st);
+  if (p.B <= 1) return launch_rows_b<TO, GLU, NB, 1, RHD, KVO>(p, st);
+  if (p.B <= 2) return launch_rows_b<TO, GLU, NB, 2, RHD, KVO>(p, st);
+  if (p.B <= 4) return launch_rows_b<TO, GLU, NB, 4, RHD, KVO>(p, st);
+  if (p.B <= 8) return launch_rows_b<TO, GLU, NB, 8, RHD, KVO>(p, st);
+  return launch_rows_b<TO, GLU, NB, 16, RHD, KVO>(p, st);
 }
 
 template <bool GLU>
@@ -996,6 +1050,23 @@ extern "C" int vg_decode_qkv_rope_rows(const void* x, int64_t ldx, const void* W
                 rope_cs, pos, k_slots, v_slots, slot_stride, row0, slot_rows, H, Hkv};
   hipStream_t st = (hipStream_t)stream;
   return K == 4096 ? launch_rows_nb<bf16_t, false, 2, 64>(p, st) : launch_rows_nb<bf16_t, false, 1, 64>(p, st);
+}
+
+// vg_decode_qkv_rope_rows with e4m3 slots: slot_stride in elements = bytes (a multiple of 8, as the attention's loads need)
+extern "C" int vg_decode_qkv_rope_rows_kv8(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out,
+                                           int64_t ldq, uint8_t* k_slots, uint8_t* v_slots, int64_t slot_stride, int row0, int slot_rows,
+                                           const float* rope_cs, const int* pos, int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream) {
+  VG_CHECK(x && Wqkv && q_out && k_slots && v_slots && rope_cs && pos && B >= 1 && B <= 16 && slot_rows > 0, VG_ERR_ARG,
+           "vg_decode_qkv_rope_rows_kv8: bad args B=%d slot_rows=%d", B, slot_rows);
+  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
+           "vg_decode_qkv_rope_rows_kv8: H=%d Hkv=%d D=%d K=%d dtype=%d not covered", H, Hkv, D, K, dtype);
+  VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)Wqkv) | ((uintptr_t)norm_w)) & 15) == 0 && slot_stride % 8 == 0 &&
+               slot_stride >= (int64_t)slot_rows * Hkv * D, VG_ERR_ARG,
+           "vg_decode_qkv_rope_rows_kv8: alignment (16 bytes; ldx / ldw / slot_stride multiples of 8; slots must not overlap)");
+  DecRowsArgs p{x, ldx, Wqkv, ldw, q_out, ldq, norm_w, eps, nullptr, 0, (H + 2 * Hkv) * D, K, B, 1, 1,
+                rope_cs, pos, k_slots, v_slots, slot_stride, row0, slot_rows, H, Hkv};
+  hipStream_t st = (hipStream_t)stream;
+  return K == 4096 ? launch_rows_nb<bf16_t, false, 2, 64, kv8_t>(p, st) : launch_rows_nb<bf16_t, false, 1, 64, kv8_t>(p, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1245,33 +1316,11 @@ template <> __device__ __forceinline__ void st_agent_elt<bf16_t>(bf16_t* p, floa
 // the cache holds OCP e4m3 codes, one byte per element and no scale, in the same [max_len, Hkv, D] layout; a chunk is still KPC = 8 elements, so
 // 8 bytes, and every (wave, chunk, lane) assignment, fmaf chain and reduction below is the bf16 body's.  e4m3 -> fp32 is exact and every e4m3
 // value is a bf16 value, so the body computes bit for bit what the bf16 body computes on the dequantised cache.
-struct kv8_t { uint8_t b; };
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+// (kv8_t, kv8_unpack8: vg_common.h; the quantiser kv8_pack4: above, beside the rope epilogues that append such rows)
 template <typename KV> struct dec_kv { typedef u32x4_t reg_t; };
 template <> struct dec_kv<kv8_t> { typedef u32x2_t reg_t; };
 template <typename KV> __device__ __forceinline__ void dec_kv_unpack(const typename dec_kv<KV>::reg_t& v, float* f) { dec_unpack<KV>(v, f); }
-template <> __device__ __forceinline__ void dec_kv_unpack<kv8_t>(const u32x2_t& v, float* f) {
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[e], true);
-    f[4 * e] = lo[0]; f[4 * e + 1] = lo[1]; f[4 * e + 2] = hi[0]; f[4 * e + 3] = hi[1];
-  }
-}
-// The e4m3 code of a bf16 value held in fp32: clamp to +-448 in fp32, then round to nearest even — bit for bit
-// x.float().clamp(-448, 448).to(torch.float8_e4m3fn).  A NaN keeps its sign and becomes the NaN code (0x7f / 0xff): the clamp must not eat it.
-__device__ __forceinline__ float kv8_clamp(float v) { return v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
-__device__ __forceinline__ uint32_t kv8_fix_nan(uint32_t w, float v, int byte) {
-  if (v != v) w = (w & ~(0xffu << (8 * byte))) | ((0x7fu | ((__float_as_uint(v) >> 24) & 0x80u)) << (8 * byte));
-  return w;
-}
-__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a), kv8_clamp(b), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(c), kv8_clamp(d), w, true);
-  uint32_t u = (uint32_t)w;
-  u = kv8_fix_nan(u, a, 0); u = kv8_fix_nan(u, b, 1); u = kv8_fix_nan(u, c, 2); u = kv8_fix_nan(u, d, 3);
-  return u;
-}
+template <> __device__ __forceinline__ void dec_kv_unpack<kv8_t>(const u32x2_t& v, float* f) { kv8_unpack8(v, f); }
 
 // DT = compile-time head_dim (0 = run-time p.D): with it every load loop below has a constant trip count, so the
 // kernel is straight-line up to the first wait and the compiler's vmcnt bookkeeping stays exact.

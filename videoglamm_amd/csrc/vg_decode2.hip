@@ -11,6 +11,9 @@
 // r05 timeline of the kernel this replaces: RoPE phase -> K/V fetch -> q.k (LDS) -> softmax (LDS) -> p.v (LDS) -> publish (4-byte stores)
 // -> ticket -> merge (4-byte loads of 27 partials): 18.8 us per layer for 14 MB of K / V.
 //
+// vg_decode_attention2_kv8 / _rows_kv8 (kv_cache = "fp8_rope"): the same kernel with the K/V storage parameter KV = kv8_t — e4m3 codes, 8 bytes
+// per lane and row, converted exactly on the way to the same dot8_bf16 / fmaf lines; bit-identical to the bf16 kernel on the dequantised caches.
+//
 // vg_decode_advance: what the host did between two steps — apply a forced token, record the emitted and the raw token, bump the position —
 // so that step k + 1 can be enqueued before token k has been read back; and the current position's cos / sin row for vg_decode_qkv_rope.
 #include "vg_common.h"
@@ -37,18 +40,40 @@ __device__ __forceinline__ float dot8_bf16(const u32x4_t& a, const u32x4_t& b, f
 }
 
 struct DecAttn2Args {
-  const bf16_t* q; const bf16_t* kc; const bf16_t* vc; bf16_t* o;
+  const bf16_t* q; const void* kc; const void* vc; bf16_t* o;      // kc / vc / ks / vs: elements of the kernel's KV type
   float* ws; int* cnt; const int* pos_dev;
   int Hkv, max_len, nsplit, window; float scale; int64_t ws_bytes;
   // ROWS form (vg_decode_attention2_rows): row b = blockIdx.z has its own query / output row, position pos_dev[b], counters and partials; key
   // blocks from row0 (a multiple of the keys per workgroup) on come from slot b: ks / vs + b * slot_stride, rows [row0, row0 + slot_rows)
-  const bf16_t* ks; const bf16_t* vs; int64_t slot_stride; int row0, slot_rows;
+  const void* ks; const void* vs; int64_t slot_stride; int row0, slot_rows;
 };
 
 constexpr int A2_D = 128, A2_PS = 132;      // partial row: 128 accumulators, max, sum, 2 pad (16-byte rows)
 
-template <int G, int NW, bool ROWS = false>
+// K/V storage of the kernel (as dec_attn_body's KV in vg_decode.hip).  KV = bf16_t: a lane's chunk of 8 elements is 16 bytes.  KV = kv8_t (the fp8 K/V
+// cache on the rope step, kv_cache = "fp8_rope"): the caches and slots hold e4m3 codes in the same [rows, Hkv, D] layout, the chunk is 8
+// bytes — 16 lanes x 8 B = one 128-byte row, still four rows per load instruction — and p.kc / vc / ks / vs / slot_stride count bytes.  a2_k turns a
+// K chunk into the four packed-bf16 dwords dot8_bf16 takes (dword e = elements 2e, 2e + 1; v_cvt_scalef32_pk_bf16_fp8 with scale 1.0: every e4m3
+// value is a bf16 value), a2_v a V chunk into the eight floats of the fmaf chains (exact).  Nothing else in the kernel knows the storage, so it
+// computes bit for bit what the bf16 kernel computes on the dequantised caches.
+template <typename KV> struct a2_kv { typedef u32x4_t reg_t; };
+template <> struct a2_kv<kv8_t> { typedef u32x2_t reg_t; };
+__device__ __forceinline__ const u32x4_t& a2_k(const u32x4_t& v) { return v; }
+__device__ __forceinline__ u32x4_t a2_k(const u32x2_t& v) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, true))};
+}
+__device__ __forceinline__ void a2_v(const u32x4_t& v, float* vf) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { vf[2 * e] = __uint_as_float(v[e] << 16); vf[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u); }
+}
+__device__ __forceinline__ void a2_v(const u32x2_t& v, float* vf) { kv8_unpack8(v, vf); }
+
+template <int G, int NW, bool ROWS = false, typename KV = bf16_t>
 __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
+  typedef typename a2_kv<KV>::reg_t kvreg_t;
   extern __shared__ __attribute__((aligned(16))) char a2_smem[];
   __shared__ int ticket;
   constexpr int KW = NW * 32;                // keys per workgroup
@@ -59,24 +84,25 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   const int j0 = s * KW + wave * 32;
 
   // ---- 1. every load up front; none of the addresses needs the position
-  u32x4_t qv[G], kreg[8], vreg[8];
+  u32x4_t qv[G];
+  kvreg_t kreg[8], vreg[8];
   const bf16_t* qrow = p.q + (int64_t)b * p.Hkv * G * A2_D;
 #pragma unroll
   for (int g = 0; g < G; ++g) qv[g] = *(const u32x4_t*)(qrow + (int64_t)(kvh * G + g) * A2_D + c * 8);
   const int64_t rs = (int64_t)p.Hkv * A2_D;
-  const bf16_t* kb = p.kc + (int64_t)kvh * A2_D + c * 8;
-  const bf16_t* vb = p.vc + (int64_t)kvh * A2_D + c * 8;
+  const KV* kb = (const KV*)p.kc + (int64_t)kvh * A2_D + c * 8;
+  const KV* vb = (const KV*)p.vc + (int64_t)kvh * A2_D + c * 8;
   int jb = j0, jlim = p.max_len;
   if (ROWS && s * KW >= p.row0) {            // a per-slot key block
-    kb = p.ks + b * p.slot_stride + (int64_t)kvh * A2_D + c * 8;
-    vb = p.vs + b * p.slot_stride + (int64_t)kvh * A2_D + c * 8;
+    kb = (const KV*)p.ks + b * p.slot_stride + (int64_t)kvh * A2_D + c * 8;
+    vb = (const KV*)p.vs + b * p.slot_stride + (int64_t)kvh * A2_D + c * 8;
     jb = j0 - p.row0;
     jlim = p.slot_rows;
   }
 #pragma unroll
-  for (int i = 0; i < 8; ++i) kreg[i] = *(const u32x4_t*)(kb + (int64_t)min(jb + 4 * i + r, jlim - 1) * rs);
+  for (int i = 0; i < 8; ++i) kreg[i] = *(const kvreg_t*)(kb + (int64_t)min(jb + 4 * i + r, jlim - 1) * rs);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) vreg[i] = *(const u32x4_t*)(vb + (int64_t)min(jb + 4 * i + r, jlim - 1) * rs);
+  for (int i = 0; i < 8; ++i) vreg[i] = *(const kvreg_t*)(vb + (int64_t)min(jb + 4 * i + r, jlim - 1) * rs);
   const int pos = p.pos_dev[b];
   const int lo = p.window > 0 ? max(0, pos + 1 - p.window) : 0;
   // ROWS: a position past the grid's bound (the caller's n_bound) would leave splits that never arrive and the counter short of nact; the
@@ -88,9 +114,11 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   // ---- 2. scores of the wave's 32 keys x G heads, softmax in registers
   float sc[G][8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+  for (int i = 0; i < 8; ++i) {
+    const auto& kv = a2_k(kreg[i]);
 #pragma unroll
-    for (int g = 0; g < G; ++g) sc[g][i] = row16_sum(dot8_bf16(kreg[i], qv[g], 0.f)) * p.scale;
+    for (int g = 0; g < G; ++g) sc[g][i] = row16_sum(dot8_bf16(kv, qv[g], 0.f)) * p.scale;
+  }
   float mw[G], lw[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -122,8 +150,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     float vf[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { vf[2 * e] = __uint_as_float(vreg[i][e] << 16); vf[2 * e + 1] = __uint_as_float(vreg[i][e] & 0xffff0000u); }
+    a2_v(vreg[i], vf);
 #pragma unroll
     for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -237,17 +264,29 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
   if (tid == 0) __hip_atomic_store(&p.cnt[hb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int G, int NW, bool ROWS = false>
+template <int G, int NW, bool ROWS, typename KV>
 static int launch_attn2(const DecAttn2Args& p, hipStream_t st, int B = 1) {
   const size_t lds = sizeof(float) * ((size_t)NW * 4 * G * A2_D + NW * G * 2);
   static size_t cap = 64 * 1024;
   if (lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_attn2_kernel<G, NW, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)decode_attn2_kernel<G, NW, ROWS, KV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     cap = lds;
   }
-  decode_attn2_kernel<G, NW, ROWS><<<dim3(p.nsplit, p.Hkv, B), NW * 64, lds, st>>>(p);
+  decode_attn2_kernel<G, NW, ROWS, KV><<<dim3(p.nsplit, p.Hkv, B), NW * 64, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
+}
+
+template <bool ROWS, typename KV>
+static int launch_attn2_g(const DecAttn2Args& p, int G, int keys_per_wg, hipStream_t st, int B = 1) {
+#define VG_A2(GG) return keys_per_wg == 256 ? launch_attn2<GG, 8, ROWS, KV>(p, st, B) : launch_attn2<GG, 4, ROWS, KV>(p, st, B)
+  switch (G) {
+    case 1: VG_A2(1);
+    case 2: VG_A2(2);
+    case 4: VG_A2(4);
+    default: VG_A2(8);
+  }
+#undef VG_A2
 }
 
 extern "C" int vg_decode_attention2_supported(int H, int Hkv, int D, int dtype) {
@@ -256,30 +295,41 @@ extern "C" int vg_decode_attention2_supported(int H, int Hkv, int D, int dtype) 
   return G == 1 || G == 2 || G == 4 || G == 8;
 }
 
-extern "C" int vg_decode_attention2(const void* q, const void* k_cache, const void* v_cache, void* out, int H, int Hkv, int D, int max_len,
-                                    int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg, int dtype,
-                                    vg_stream_t stream) {
-  VG_CHECK(q && k_cache && v_cache && out && pos_dev && workspace, VG_ERR_ARG, "vg_decode_attention2: null pointer");
-  VG_CHECK(vg_decode_attention2_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "vg_decode_attention2: H=%d Hkv=%d D=%d dtype=%d not covered", H, Hkv, D, dtype);
-  VG_CHECK(keys_per_wg == 128 || keys_per_wg == 256, VG_ERR_ARG, "vg_decode_attention2: keys_per_wg %d not in {128, 256}", keys_per_wg);
-  VG_CHECK(max_len > 0 && window >= 0, VG_ERR_ARG, "vg_decode_attention2: bad max_len / window");
-  VG_CHECK((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0, VG_ERR_ARG,
-           "vg_decode_attention2: 16-byte alignment");
+// fn: the entry point's name for the messages; the caches' alignment is one chunk of the KV type (16 bytes of bf16, 8 bytes of e4m3 codes)
+template <typename KV>
+static int decode_attention2(const char* fn, const void* q, const void* k_cache, const void* v_cache, void* out, int H, int Hkv, int D, int max_len, int window,
+                             float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg, int dtype, vg_stream_t stream) {
+  constexpr int KVA = 8 * (int)sizeof(KV);
+  VG_CHECK(q && k_cache && v_cache && out && pos_dev && workspace, VG_ERR_ARG, "%s: null pointer", fn);
+  VG_CHECK(vg_decode_attention2_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "%s: H=%d Hkv=%d D=%d dtype=%d not covered", fn, H, Hkv, D, dtype);
+  VG_CHECK(keys_per_wg == 128 || keys_per_wg == 256, VG_ERR_ARG, "%s: keys_per_wg %d not in {128, 256}", fn, keys_per_wg);
+  VG_CHECK(max_len > 0 && window >= 0, VG_ERR_ARG, "%s: bad max_len / window", fn);
+  VG_CHECK((((uintptr_t)q | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 && (((uintptr_t)k_cache | (uintptr_t)v_cache) & (KVA - 1)) == 0, VG_ERR_ARG,
+           "%s: 16-byte alignment (caches: %d bytes)", fn, KVA);
   const int G = H / Hkv;
   const int nsplit = (max_len + keys_per_wg - 1) / keys_per_wg;
   const int64_t need = (int64_t)Hkv * nsplit * G * A2_PS + Hkv;
-  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention2: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
-  DecAttn2Args p{(const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_cache, (bf16_t*)out, workspace, (int*)(workspace + (ws_floats - Hkv)), pos_dev,
+  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "%s: workspace %lld < %lld floats", fn, (long long)ws_floats, (long long)need);
+  DecAttn2Args p{(const bf16_t*)q, k_cache, v_cache, (bf16_t*)out, workspace, (int*)(workspace + (ws_floats - Hkv)), pos_dev,
                  Hkv, max_len, nsplit, window, scale, ws_floats * 4};
-  hipStream_t st = (hipStream_t)stream;
-#define VG_A2(GG) return keys_per_wg == 256 ? launch_attn2<GG, 8>(p, st) : launch_attn2<GG, 4>(p, st)
-  switch (G) {
-    case 1: VG_A2(1);
-    case 2: VG_A2(2);
-    case 4: VG_A2(4);
-    default: VG_A2(8);
-  }
-#undef VG_A2
+  return launch_attn2_g<false, KV>(p, G, keys_per_wg, (hipStream_t)stream);
+}
+
+extern "C" int vg_decode_attention2(const void* q, const void* k_cache, const void* v_cache, void* out, int H, int Hkv, int D, int max_len,
+                                    int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg, int dtype,
+                                    vg_stream_t stream) {
+  return decode_attention2<bf16_t>("vg_decode_attention2", q, k_cache, v_cache, out, H, Hkv, D, max_len, window, scale, pos_dev, workspace, ws_floats,
+                                   keys_per_wg, dtype, stream);
+}
+
+// vg_decode_attention2 on e4m3 caches (kv8_t above): bf16 q / out, the same workspace, the same shapes
+extern "C" int vg_decode_attention2_kv8_supported(int H, int Hkv, int D, int dtype) { return vg_decode_attention2_supported(H, Hkv, D, dtype); }
+
+extern "C" int vg_decode_attention2_kv8(const void* q, const uint8_t* k_cache, const uint8_t* v_cache, void* out, int H, int Hkv, int D, int max_len,
+                                        int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg, int dtype,
+                                        vg_stream_t stream) {
+  return decode_attention2<kv8_t>("vg_decode_attention2_kv8", q, k_cache, v_cache, out, H, Hkv, D, max_len, window, scale, pos_dev, workspace, ws_floats,
+                                  keys_per_wg, dtype, stream);
 }
 
 // B query rows at once (the batched multi-prompt decode step): grid z = row.  Row b is decode_attn2_kernel's row b alone — the same
@@ -293,32 +343,43 @@ extern "C" int64_t vg_decode_attention2_rows_ws_floats(int H, int Hkv, int D, in
   return (int64_t)B * Hkv * nsplit * (H / Hkv) * A2_PS + (int64_t)B * Hkv;
 }
 
+template <typename KV>
+static int decode_attention2_rows(const char* fn, const void* q, const void* k_cache, const void* v_cache, int max_len, const void* k_slots, const void* v_slots,
+                                  int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D, int n_bound, int window, float scale,
+                                  const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg, int B, int dtype, vg_stream_t stream) {
+  constexpr int KVA = 8 * (int)sizeof(KV);
+  VG_CHECK(q && k_cache && v_cache && k_slots && v_slots && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG, "%s: bad args", fn);
+  VG_CHECK(vg_decode_attention2_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "%s: H=%d Hkv=%d D=%d dtype=%d not covered", fn, H, Hkv, D, dtype);
+  VG_CHECK(keys_per_wg == 128 || keys_per_wg == 256, VG_ERR_ARG, "%s: keys_per_wg %d not in {128, 256}", fn, keys_per_wg);
+  VG_CHECK(row0 >= 0 && row0 % keys_per_wg == 0 && row0 <= max_len && slot_rows > 0 && n_bound > row0 && n_bound <= row0 + slot_rows && window >= 0, VG_ERR_ARG,
+           "%s: row0=%d (a multiple of %d, <= max_len %d), slot_rows=%d, n_bound=%d in (row0, row0 + slot_rows]", fn, row0, keys_per_wg, max_len,
+           slot_rows, n_bound);
+  VG_CHECK((((uintptr_t)q | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 &&
+               (((uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k_slots | (uintptr_t)v_slots) & (KVA - 1)) == 0 && slot_stride % 8 == 0, VG_ERR_ARG,
+           "%s: 16-byte alignment (caches and slots: %d bytes; slot_stride a multiple of 8)", fn, KVA);
+  const int64_t need = vg_decode_attention2_rows_ws_floats(H, Hkv, D, n_bound, keys_per_wg, B);
+  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "%s: workspace %lld < %lld floats", fn, (long long)ws_floats, (long long)need);
+  const int G = H / Hkv;
+  const int nsplit = (n_bound + keys_per_wg - 1) / keys_per_wg;
+  DecAttn2Args p{(const bf16_t*)q, k_cache, v_cache, (bf16_t*)out, workspace, (int*)(workspace + (ws_floats - (int64_t)B * Hkv)), pos,
+                 Hkv, max_len, nsplit, window, scale, ws_floats * 4, k_slots, v_slots, slot_stride, row0, slot_rows};
+  return launch_attn2_g<true, KV>(p, G, keys_per_wg, (hipStream_t)stream, B);
+}
+
 extern "C" int vg_decode_attention2_rows(const void* q, const void* k_cache, const void* v_cache, int max_len, const void* k_slots, const void* v_slots,
                                          int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D, int n_bound, int window, float scale,
                                          const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg, int B, int dtype, vg_stream_t stream) {
-  VG_CHECK(q && k_cache && v_cache && k_slots && v_slots && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_attention2_rows: bad args");
-  VG_CHECK(vg_decode_attention2_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "vg_decode_attention2_rows: H=%d Hkv=%d D=%d dtype=%d not covered", H, Hkv, D, dtype);
-  VG_CHECK(keys_per_wg == 128 || keys_per_wg == 256, VG_ERR_ARG, "vg_decode_attention2_rows: keys_per_wg %d not in {128, 256}", keys_per_wg);
-  VG_CHECK(row0 >= 0 && row0 % keys_per_wg == 0 && row0 <= max_len && slot_rows > 0 && n_bound > row0 && n_bound <= row0 + slot_rows && window >= 0, VG_ERR_ARG,
-           "vg_decode_attention2_rows: row0=%d (a multiple of %d, <= max_len %d), slot_rows=%d, n_bound=%d in (row0, row0 + slot_rows]", row0, keys_per_wg, max_len,
-           slot_rows, n_bound);
-  VG_CHECK((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k_slots | (uintptr_t)v_slots | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 &&
-               slot_stride % 8 == 0, VG_ERR_ARG, "vg_decode_attention2_rows: 16-byte alignment");
-  const int64_t need = vg_decode_attention2_rows_ws_floats(H, Hkv, D, n_bound, keys_per_wg, B);
-  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention2_rows: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
-  const int G = H / Hkv;
-  const int nsplit = (n_bound + keys_per_wg - 1) / keys_per_wg;
-  DecAttn2Args p{(const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_cache, (bf16_t*)out, workspace, (int*)(workspace + (ws_floats - (int64_t)B * Hkv)), pos,
-                 Hkv, max_len, nsplit, window, scale, ws_floats * 4, (const bf16_t*)k_slots, (const bf16_t*)v_slots, slot_stride, row0, slot_rows};
-  hipStream_t st = (hipStream_t)stream;
-#define VG_A2R(GG) return keys_per_wg == 256 ? launch_attn2<GG, 8, true>(p, st, B) : launch_attn2<GG, 4, true>(p, st, B)
-  switch (G) {
-    case 1: VG_A2R(1);
-    case 2: VG_A2R(2);
-    case 4: VG_A2R(4);
-    default: VG_A2R(8);
-  }
-#undef VG_A2R
+  return decode_attention2_rows<bf16_t>("vg_decode_attention2_rows", q, k_cache, v_cache, max_len, k_slots, v_slots, slot_stride, row0, slot_rows, out, H, Hkv,
+                                        D, n_bound, window, scale, pos, workspace, ws_floats, keys_per_wg, B, dtype, stream);
+}
+
+// kv8: the shared caches and the slots hold e4m3 codes (slot_stride in elements = bytes)
+extern "C" int vg_decode_attention2_rows_kv8(const void* q, const uint8_t* k_cache, const uint8_t* v_cache, int max_len, const uint8_t* k_slots,
+                                             const uint8_t* v_slots, int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D,
+                                             int n_bound, int window, float scale, const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg,
+                                             int B, int dtype, vg_stream_t stream) {
+  return decode_attention2_rows<kv8_t>("vg_decode_attention2_rows_kv8", q, k_cache, v_cache, max_len, k_slots, v_slots, slot_stride, row0, slot_rows, out, H,
+                                       Hkv, D, n_bound, window, scale, pos, workspace, ws_floats, keys_per_wg, B, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

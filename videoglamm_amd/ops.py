@@ -817,28 +817,59 @@ def decode_rope_path(H, Hkv, D, K, dtype):
     return bool(lib.vg_decode_qkv_rope_supported(H, Hkv, D, K, dt) and lib.vg_decode_attention2_supported(H, Hkv, D, dt))
 
 
+def decode_rope_path_kv8(H, Hkv, D, K, dtype):
+    """True when vg_decode_qkv_rope_kv8 + vg_decode_attention2_kv8 cover this shape: decode_rope_path's shapes in bf16 (kv_cache = "fp8_rope")."""
+    lib = _lib.load()
+    return dtype == torch.bfloat16 and bool(lib.vg_decode_qkv_rope_supported(H, Hkv, D, K, BF16) and lib.vg_decode_attention2_kv8_supported(H, Hkv, D, BF16))
+
+
 def decode_qkv_rope(x, wqkv, norm_w, eps, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, out=None):
     """RMSNorm -> q|k|v GEMV -> RoPE -> KV append of ONE row (vg_decode_qkv_rope): -> rotated q [1, H*D]; k_cache / v_cache row *pos_dev written."""
+    assert k_cache.dtype == x.dtype
+    return _decode_qkv_rope("vg_decode_qkv_rope", x, wqkv, norm_w, eps, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, out)
+
+
+def decode_qkv_rope_kv8(x, wqkv, norm_w, eps, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, out=None):
+    """decode_qkv_rope with uint8 e4m3 caches (vg_decode_qkv_rope_kv8): the same q; row *pos_dev of the caches = kv_quantize_reference of the bf16
+    rows decode_qkv_rope writes, every other byte untouched."""
+    assert x.dtype == torch.bfloat16 and k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8
+    assert k_cache.shape[1:] == (Hkv, D) and v_cache.shape == k_cache.shape
+    return _decode_qkv_rope("vg_decode_qkv_rope_kv8", x, wqkv, norm_w, eps, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, out)
+
+
+def _decode_qkv_rope(fn, x, wqkv, norm_w, eps, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, out):
     lib = _lib.load()
     K = x.shape[-1]
     assert x.numel() == K and x.is_contiguous() and wqkv.stride(1) == 1 and wqkv.shape == ((H + 2 * Hkv) * D, K)
-    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.dtype == x.dtype and pos_dev.dtype == torch.int32
+    assert k_cache.is_contiguous() and v_cache.is_contiguous() and pos_dev.dtype == torch.int32
     assert rope_cs.dtype == torch.float32 and rope_cs.numel() == D and rope_cs.is_contiguous()
     q = out if out is not None else torch.empty(1, H * D, dtype=x.dtype, device=x.device)
-    rc = lib.vg_decode_qkv_rope(_p(x), _p(wqkv), wqkv.stride(0), _p(_f32(norm_w)), float(eps), _p(q), _p(k_cache), _p(v_cache), _p(rope_cs),
-                                _p(pos_dev), H, Hkv, D, K, _dt(x), _stream())
-    _lib.check(rc, "vg_decode_qkv_rope")
+    rc = getattr(lib, fn)(_p(x), _p(wqkv), wqkv.stride(0), _p(_f32(norm_w)), float(eps), _p(q), _p(k_cache), _p(v_cache), _p(rope_cs),
+                          _p(pos_dev), H, Hkv, D, K, _dt(x), _stream())
+    _lib.check(rc, fn)
     return q
 
 
 def decode_attention2(q, k_cache, v_cache, H, Hkv, D, pos_dev, scale, ws, window=0, keys_per_wg=256):
     """attention of the one new (pre-rotated) query row against caches that already hold its key / value row (vg_decode_attention2)."""
+    return _decode_attention2("vg_decode_attention2", q, k_cache, v_cache, H, Hkv, D, pos_dev, scale, ws, window, keys_per_wg)
+
+
+def decode_attention2_kv8(q, k_cache, v_cache, H, Hkv, D, pos_dev, scale, ws, window=0, keys_per_wg=256):
+    """decode_attention2 on uint8 e4m3 caches (vg_decode_attention2_kv8): bit-identical to decode_attention2 on kv_dequantize of them.  The new
+    token's row is in the caches already, so it attends to its own key / value quantised.  ws: decode_attention_workspace."""
+    assert q.dtype == torch.bfloat16 and k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8
+    assert k_cache.shape[1:] == (Hkv, D) and v_cache.shape == k_cache.shape
+    return _decode_attention2("vg_decode_attention2_kv8", q, k_cache, v_cache, H, Hkv, D, pos_dev, scale, ws, window, keys_per_wg)
+
+
+def _decode_attention2(fn, q, k_cache, v_cache, H, Hkv, D, pos_dev, scale, ws, window, keys_per_wg):
     lib = _lib.load()
     assert q.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous() and pos_dev.dtype == torch.int32
     out = torch.empty(1, H * D, dtype=q.dtype, device=q.device)
-    rc = lib.vg_decode_attention2(_p(q), _p(k_cache), _p(v_cache), _p(out), H, Hkv, D, k_cache.shape[0], int(window), float(scale), _p(pos_dev),
-                                  _p(ws), ws.numel(), int(keys_per_wg), _dt(q), _stream())
-    _lib.check(rc, "vg_decode_attention2")
+    rc = getattr(lib, fn)(_p(q), _p(k_cache), _p(v_cache), _p(out), H, Hkv, D, k_cache.shape[0], int(window), float(scale), _p(pos_dev),
+                          _p(ws), ws.numel(), int(keys_per_wg), _dt(q), _stream())
+    _lib.check(rc, fn)
     return out
 
 
@@ -1072,15 +1103,26 @@ def decode_gemv_w4_rows(x, w4, norm_w=None, eps=0.0, residual=None, glu=False, o
 def decode_qkv_rope_rows(x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out=None):
     """decode_qkv_rope on each row of x [B,K]: row b at position pos_dev[b] with rope_cs[b], its K / V rows into slot b of k_slots / v_slots
     ([B, rows, Hkv, D], row j of the sequence at j - row0) -> rotated q [B, H*D]."""
+    assert k_slots.dtype == x.dtype
+    return _decode_qkv_rope_rows("vg_decode_qkv_rope_rows", x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out)
+
+
+def decode_qkv_rope_rows_kv8(x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out=None):
+    """decode_qkv_rope_rows with uint8 e4m3 slots (vg_decode_qkv_rope_rows_kv8): row b is decode_qkv_rope_kv8 on that row alone."""
+    assert x.dtype == torch.bfloat16 and k_slots.dtype == torch.uint8 and v_slots.dtype == torch.uint8
+    return _decode_qkv_rope_rows("vg_decode_qkv_rope_rows_kv8", x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out)
+
+
+def _decode_qkv_rope_rows(fn, x, wqkv, norm_w, eps, k_slots, v_slots, row0, rope_cs, pos_dev, H, Hkv, D, out):
     lib = _lib.load()
     B, K = x.shape
     assert x.stride(1) == 1 and wqkv.stride(1) == 1 and wqkv.shape == ((H + 2 * Hkv) * D, K) and pos_dev.dtype == torch.int32 and pos_dev.numel() >= B
     assert k_slots.is_contiguous() and v_slots.is_contiguous() and k_slots.shape[0] >= B and k_slots.shape[2:] == (Hkv, D) and k_slots.shape == v_slots.shape
     assert rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and rope_cs.shape[-1] == D and rope_cs.shape[0] >= B
     q = out if out is not None else torch.empty(B, H * D, dtype=x.dtype, device=x.device)
-    rc = lib.vg_decode_qkv_rope_rows(_p(x), x.stride(0), _p(wqkv), wqkv.stride(0), _p(_f32(norm_w)), float(eps), _p(q), q.stride(0), _p(k_slots), _p(v_slots),
-                                     k_slots.stride(0), int(row0), k_slots.shape[1], _p(rope_cs), _p(pos_dev), H, Hkv, D, K, B, _dt(x), _stream())
-    _lib.check(rc, "vg_decode_qkv_rope_rows")
+    rc = getattr(lib, fn)(_p(x), x.stride(0), _p(wqkv), wqkv.stride(0), _p(_f32(norm_w)), float(eps), _p(q), q.stride(0), _p(k_slots), _p(v_slots),
+                          k_slots.stride(0), int(row0), k_slots.shape[1], _p(rope_cs), _p(pos_dev), H, Hkv, D, K, B, _dt(x), _stream())
+    _lib.check(rc, fn)
     return q
 
 
@@ -1093,15 +1135,29 @@ def decode_attention2_rows_workspace(H, Hkv, D, n_bound, keys_per_wg, B, device)
 
 def decode_attention2_rows(q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, D, pos_dev, n_bound, scale, ws, window=0, keys_per_wg=256):
     """decode_attention2 on each row of q [B, H*D]: keys [0, row0) from the shared caches, [row0, pos_dev[b]] from slot b -> [B, H*D]."""
+    return _decode_attention2_rows("vg_decode_attention2_rows", q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, D, pos_dev, n_bound, scale, ws,
+                                   window, keys_per_wg)
+
+
+def decode_attention2_rows_kv8(q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, D, pos_dev, n_bound, scale, ws, window=0, keys_per_wg=256):
+    """decode_attention2_rows with uint8 e4m3 shared caches and slots (vg_decode_attention2_rows_kv8): each row bit-identical to
+    decode_attention2_kv8 on it alone.  ws: decode_attention2_rows_workspace."""
+    assert q.dtype == torch.bfloat16 and all(t.dtype == torch.uint8 for t in (k_cache, v_cache, k_slots, v_slots))
+    assert k_cache.shape[1:] == (Hkv, D) and v_cache.shape == k_cache.shape and k_slots.shape[2:] == (Hkv, D) and v_slots.shape == k_slots.shape
+    return _decode_attention2_rows("vg_decode_attention2_rows_kv8", q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, D, pos_dev, n_bound, scale, ws,
+                                   window, keys_per_wg)
+
+
+def _decode_attention2_rows(fn, q, k_cache, v_cache, k_slots, v_slots, row0, H, Hkv, D, pos_dev, n_bound, scale, ws, window, keys_per_wg):
     lib = _lib.load()
     B = q.shape[0]
     assert q.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous() and k_slots.is_contiguous() and v_slots.is_contiguous()
     assert pos_dev.dtype == torch.int32 and k_slots.shape[0] >= B
     out = torch.empty(B, H * D, dtype=q.dtype, device=q.device)
-    rc = lib.vg_decode_attention2_rows(_p(q), _p(k_cache), _p(v_cache), k_cache.shape[0], _p(k_slots), _p(v_slots), k_slots.stride(0), int(row0), k_slots.shape[1],
-                                       _p(out), H, Hkv, D, int(n_bound), int(window), float(scale), _p(pos_dev), _p(ws), ws.numel(), int(keys_per_wg), B, _dt(q),
-                                       _stream())
-    _lib.check(rc, "vg_decode_attention2_rows")
+    rc = getattr(lib, fn)(_p(q), _p(k_cache), _p(v_cache), k_cache.shape[0], _p(k_slots), _p(v_slots), k_slots.stride(0), int(row0), k_slots.shape[1],
+                          _p(out), H, Hkv, D, int(n_bound), int(window), float(scale), _p(pos_dev), _p(ws), ws.numel(), int(keys_per_wg), B, _dt(q),
+                          _stream())
+    _lib.check(rc, fn)
     return out
 
 

@@ -205,33 +205,47 @@ def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, suppo
 
 
 def kv_cache_mode(value, dtype, device_type, fused, env):
-    """cfg["llm"]["kv_cache"] -> True when the decode step keeps its keys / values as e4m3 codes, False for "bf16" (the default: the
-    cache holds the model's dtype), or ValueError saying why this decoder cannot take the mode.  dtype / device_type: the model's; fused: the fused
-    decode kernels cover the decoder (LlamaDecoder.fused_decode); env: the environment.  Pure: no device work."""
+    """cfg["llm"]["kv_cache"] -> truthy when the decode step keeps its keys / values as e4m3 codes: True for "fp8" (the
+    decode_attention form of the step at every width), the string "rope" for "fp8_rope" (the same format on the rope step: Llama-3 width);
+    False for "bf16" (the default: the cache holds the model's dtype), or ValueError saying why this decoder cannot take the mode.  dtype /
+    device_type: the model's; fused: the fused decode kernels cover the decoder (LlamaDecoder.fused_decode); env: the environment.  Pure: no
+    device work."""
     if value in (None, "bf16"):
         return False
-    if value != "fp8":
-        raise ValueError(f"cfg['llm']['kv_cache'] = {value!r}: 'bf16' (default) or 'fp8'")
+    if value not in ("fp8", "fp8_rope"):
+        raise ValueError(f"cfg['llm']['kv_cache'] = {value!r}: 'bf16' (default), 'fp8' or 'fp8_rope'")
     if dtype != torch.bfloat16:
-        raise ValueError(f"kv_cache = 'fp8' needs a bf16 model (the e4m3 cache holds quantised bf16 rows), not {dtype}")
+        raise ValueError(f"kv_cache = {value!r} needs a bf16 model (the e4m3 cache holds quantised bf16 rows), not {dtype}")
     if device_type != "cuda":
-        raise ValueError(f"kv_cache = 'fp8' runs on the GPU's decode kernels, not on device {device_type!r}")
+        raise ValueError(f"kv_cache = {value!r} runs on the GPU's decode kernels, not on device {device_type!r}")
     if not fused:
-        raise ValueError("kv_cache = 'fp8' needs the fused decode kernels (vg_decode_attention_kv8): this decoder's shape is outside them, "
-                         "or VG_DECODE_FUSED=0")
+        raise ValueError(f"kv_cache = {value!r} needs the fused decode kernels (vg_decode_attention_kv8 / vg_decode_attention2_kv8): this decoder's "
+                         "shape is outside them, or VG_DECODE_FUSED=0")
     if env.get("VG_DECODE_CHAIN", "0") != "0":
-        raise ValueError(f"kv_cache = 'fp8' does not combine with VG_DECODE_CHAIN={env.get('VG_DECODE_CHAIN')}: vg_decode_layer reads a bf16 cache")
-    return True
+        raise ValueError(f"kv_cache = {value!r} does not combine with VG_DECODE_CHAIN={env.get('VG_DECODE_CHAIN')}: vg_decode_layer reads a bf16 cache")
+    return True if value == "fp8" else "rope"
 
 
 def decode_step_form(rope_covered, attn_rows_covered, kv8=False):
     """"rope" | "attention" | None: which B-row step (RowsDecode) goes with the decoder's single-row step.  rope_covered: the single-row step may
     take the rope path (bf16 head_dim 128: Llama-3 width); attn_rows_covered: the B-row kernels cover the decode_attention step's layer (Phi-3-mini
-    width).  kv8 (the fp8 K/V cache): there is no rope path on e4m3 caches, so Llama-3 width runs the decode_attention form single-row and has
-    no B-row step — the mode is meant for the MHA model.  Pure."""
+    width).  kv8 = kv_cache_mode's answer.  True (kv_cache = "fp8"): that mode keeps off the rope path, so Llama-3 width runs the decode_attention
+    form single-row and has no B-row step — the mode is meant for the MHA model.  "rope" (kv_cache = "fp8_rope"): the mode IS the rope step on
+    e4m3 caches (rope_covered then speaks of ops.decode_rope_path_kv8) and has no other form: None where that step does not cover the decoder
+    (kv_cache_check_rope refuses such a decoder).  Pure."""
+    if kv8 == "rope":
+        return "rope" if rope_covered else None
     if rope_covered and not kv8:
         return "rope"
     return "attention" if attn_rows_covered else None
+
+
+def kv_cache_check_rope(step):
+    """ValueError when kv_cache = "fp8_rope" meets a decoder its step does not cover.  step: decode_step_form(..., kv8="rope").  Pure."""
+    if step != "rope":
+        raise ValueError("kv_cache = 'fp8_rope' is the fp8 K/V cache on the rope step (vg_decode_qkv_rope_kv8 + vg_decode_attention2_kv8: bf16, "
+                         "head_dim 128, hidden 2048 / 4096 — Llama-3 width), which does not cover this decoder (Phi-3-mini width, or "
+                         "VG_DECODE_ROPE=0): kv_cache = 'fp8' runs the decode_attention form of the step at every width")
 
 
 def kv_cache_check_gemv(decode_gemv, step):
@@ -239,7 +253,8 @@ def kv_cache_check_gemv(decode_gemv, step):
     too, and at Llama-3 width those belong to the rope step.  step: decode_step_form(..., kv8=True).  Pure."""
     if decode_gemv in ("mfma", "mfma_q") and step is None:
         raise ValueError(f"kv_cache = 'fp8' does not combine with decode_gemv = {decode_gemv!r} on this decoder: the mode's projections belong to "
-                         "the rope step (Llama-3 width), which has no fp8 K/V form; Phi-3-mini width (the decode_attention rows step) takes both")
+                         "the rope step (Llama-3 width), which this mode keeps off (kv_cache = 'fp8_rope' is that step on e4m3 caches); Phi-3-mini "
+                         "width (the decode_attention rows step) takes both")
 
 
 class DecodeProjections:
@@ -405,23 +420,28 @@ class LlamaDecoder:
         self.chain_roles, self.chain_flags, self.chain_err = 0, None, None
         # cfg["kv_cache"] == "fp8" (DESIGN 8c): the decode step reads and appends e4m3 keys / values (kc8 / vc8: one byte per element, no scale, the
         # bf16 cache's layout); kc / vc stay as the prefill's bf16 staging — a prefill attends to unquantised K/V with today's launches, then
-        # forward() quantises the rows it wrote.  The step is the decode_attention form at every width: no rope path, no chained launch
+        # forward() quantises the rows it wrote.  No chained launch.  "fp8": the step is the decode_attention form at every width (kv8 is True: the
+        # new token's K/V take part in their own step unquantised).  "fp8_rope": the rope step on the same caches (kv8 == "rope": the new token's
+        # row is in the cache before the attention reads it, so it attends to its own K/V quantised); a decoder that step does not cover is refused
         self.kv8 = kv_cache_mode(c.get("kv_cache"), dt, dev.type, self.fused_decode, os.environ)
         self.kc8 = self.vc8 = None
-        if self.kv8:
-            self.kc8 = [torch.zeros(max_len, self.Hkv, self.hd, dtype=torch.uint8, device=dev) for _ in range(c["num_layers"])]
-            self.vc8 = [torch.zeros(max_len, self.Hkv, self.hd, dtype=torch.uint8, device=dev) for _ in range(c["num_layers"])]
         self.staged = 0      # kv8: rows [0, staged) of kc / vc are what a prefill wrote; decode steps append to kc8 / vc8 only (forward())
         if self.fused_decode and dev.type == "cuda" and not self.kv8:
             self.chain_roles = min(ops.decode_layer_roles(self.H, self.Hkv, self.hd, self.D, ffn, dt), int(os.environ.get("VG_DECODE_CHAIN", "0")))
             if self.chain_roles == 2:
                 self.chain_roles = 1
         # r06: RoPE + KV append in the q|k|v GEMV's epilogue, attention as a wave-private flash pass (bf16, head_dim 128); VG_DECODE_ROPE=0 = A/B knob
+        rope_shapes = ops.decode_rope_path_kv8 if self.kv8 == "rope" else ops.decode_rope_path
         rope_covered = (self.fused_decode and dev.type == "cuda" and not self.chain_roles and os.environ.get("VG_DECODE_ROPE", "1") != "0"
-                        and ops.decode_rope_path(self.H, self.Hkv, self.hd, self.D, dt))
+                        and rope_shapes(self.H, self.Hkv, self.hd, self.D, dt))
         rows_covered = (self.fused_decode and dev.type == "cuda" and not self.chain_roles
                         and ops.decode_step_rows_supported(self.H, self.Hkv, self.hd, self.D, ffn, dt))
         step = decode_step_form(rope_covered, rows_covered, self.kv8)
+        if self.kv8 == "rope":
+            kv_cache_check_rope(step)
+        if self.kv8:
+            self.kc8 = [torch.zeros(max_len, self.Hkv, self.hd, dtype=torch.uint8, device=dev) for _ in range(c["num_layers"])]
+            self.vc8 = [torch.zeros(max_len, self.Hkv, self.hd, dtype=torch.uint8, device=dev) for _ in range(c["num_layers"])]
         self.rope_path = step == "rope"
         self.kpw2 = int(os.environ.get("VG_DEC2_KPW", "256"))
         # cfg["decode_gemv"] ("valu" | "mfma" | "mfma_q") x cfg["decode_weights"]: which kernel and stored weight each projection of the single-row
@@ -522,10 +542,12 @@ class LlamaDecoder:
             l = f"model.layers.{i}."
             if self.rope_path:
                 # norm -> q|k|v -> RoPE -> append in one launch; the attention starts on its K / V loads (4 launches per layer + the MLP's 2)
-                q = ops.decode_qkv_rope(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.kc[i], self.vc[i],
-                                        self.rope_cs, self.pos_dev, self.H, self.Hkv, self.hd)
-                o = ops.decode_attention2(q, self.kc[i], self.vc[i], self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5, self.attn_ws,
-                                          window=self.window, keys_per_wg=self.kpw2)
+                qkv_rope, attn2, kc, vc = ((ops.decode_qkv_rope_kv8, ops.decode_attention2_kv8, self.kc8, self.vc8) if self.kv8 else
+                                           (ops.decode_qkv_rope, ops.decode_attention2, self.kc, self.vc))
+                q = qkv_rope(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], kc[i], vc[i],
+                             self.rope_cs, self.pos_dev, self.H, self.Hkv, self.hd)
+                o = attn2(q, kc[i], vc[i], self.H, self.Hkv, self.hd, self.pos_dev, self.hd ** -0.5, self.attn_ws,
+                          window=self.window, keys_per_wg=self.kpw2)
                 x = pr.run("o", False, P, l, o, residual=x)
             else:
                 qkv = pr.run("qkv", False, P, l, x, norm_w=P.f32(l + "input_layernorm.weight"), eps=c["rms_eps"])
@@ -580,7 +602,8 @@ class LlamaDecoder:
         all-gathered at the end (the replicated decode continues from the last one)."""
         c = self.c
         if self.kv8:
-            raise ValueError("kv_cache = 'fp8' has no sequence-parallel prefill (forward_sharded): run the model on one GPU, or keep kv_cache = 'bf16'")
+            raise ValueError("kv_cache = 'fp8' / 'fp8_rope' has no sequence-parallel prefill (forward_sharded): run the model on one GPU, or keep "
+                             "kv_cache = 'bf16'")
         S, W, r = x.shape[0], comm.world, comm.rank
         m = -(-S // W)
         a = min(r * m, S)
@@ -717,8 +740,10 @@ class RowsDecode:
         self.attn_rows = not d.rope_path
         assert row0 % (self.ATTN_KW if self.attn_rows else d.kpw2) == 0
         rows = n_bound - row0
-        self.kv8 = bool(getattr(d, "kv8", False))       # the decoder's fp8 K/V cache: the slots hold e4m3 codes as kc8 / vc8 do
-        assert self.attn_rows or not self.kv8
+        # the decoder's fp8 K/V cache: the slots hold e4m3 codes as kc8 / vc8 do, on either form of the step ("fp8": decode_attention
+        # rows; "fp8_rope": the rope form)
+        self.kv8 = bool(getattr(d, "kv8", False))
+        assert not self.kv8 or self.attn_rows == (d.kv8 is True)
         kdt = torch.uint8 if self.kv8 else dt
         self.ks = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=kdt, device=dev) for _ in range(d.c["num_layers"])]
         self.vs = [torch.zeros(B, rows, d.Hkv, d.hd, dtype=kdt, device=dev) for _ in range(d.c["num_layers"])]
@@ -783,10 +808,12 @@ class RowsDecode:
                 o = attn(qkv, kc[i], vc[i], self.ks[i], self.vs[i], self.row0, d.cos, d.sin, d.H, d.Hkv, d.hd, self.pos,
                          self.n_bound, d.hd ** -0.5, self.attn_ws, window=d.window, kpw_min=d.kpw_min)
             else:
-                q = ops.decode_qkv_rope_rows(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i],
-                                             self.row0, self.rope_cs, self.pos, d.H, d.Hkv, d.hd)
-                o = ops.decode_attention2_rows(q, d.kc[i], d.vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
-                                               d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
+                qkv_rope, attn2, kc, vc = ((ops.decode_qkv_rope_rows_kv8, ops.decode_attention2_rows_kv8, d.kc8, d.vc8) if self.kv8 else
+                                           (ops.decode_qkv_rope_rows, ops.decode_attention2_rows, d.kc, d.vc))
+                q = qkv_rope(x, *pr.operands(P, "qkv", l), P.f32(l + "input_layernorm.weight"), c["rms_eps"], self.ks[i], self.vs[i],
+                             self.row0, self.rope_cs, self.pos, d.H, d.Hkv, d.hd)
+                o = attn2(q, kc[i], vc[i], self.ks[i], self.vs[i], self.row0, d.H, d.Hkv, d.hd, self.pos, self.n_bound,
+                          d.hd ** -0.5, self.attn_ws, window=d.window, keys_per_wg=d.kpw2)
             x = pr.run("o", True, P, l, o, residual=x)
             a, x = pr.mlp(True, P, l, x, c["rms_eps"])
         h = ops.rmsnorm(x, P.f32("model.norm.weight"), c["rms_eps"])

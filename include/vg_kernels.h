@@ -608,6 +608,19 @@ int vg_quantize_fp8_rows(const void* x, int64_t ldx, uint8_t* q, int64_t ldq, fl
 int vg_gemm_f8(const uint8_t* A8, int64_t lda, const float* a_scale, const uint8_t* W8, int64_t ldw, const float* w_scale,
                void* C, int64_t ldc, const float* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K,
                int out_dtype, int a_op, vg_stream_t stream);
+/* MXFP4 prefill GEMM (cfg prefill_gemm = "mxfp4": the LLM's MLP on the packed rows the decode step streams):
+ *   C[m,n] = a_scale[m] * sum_k e4m3(A8[m,k]) * 2^(s[n, k / 32] - 127) * e2m1(W4[n,k])  (+ R[m,n]),
+ * fp32 accumulation on v_mfma_scale_f32_32x32x64_f8f6f4 with A = e4m3 (unit scale) and B = e2m1 with the weight's e8m0 byte as its hardware block scale.
+ * A8 [M,K] (lda bytes per row) and a_scale [M] are what vg_quantize_fp8_rows produces.  W4 = the PACKED rows of vg_decode_gemv_w4 read in place: row n at
+ * W4 + n * ldw_bytes = a head of 64 * SPL scale bytes (byte lane * SPL + u = the scale of block 64 u + lane), then K / 2 code bytes, element 2j in the low
+ * nibble of byte j; no second copy of codes or scales is made.  A scale byte 0 means the block is exactly zero whatever its codes hold (as in every
+ * MXFP4 entry point).  a_op = 0: N rows of W4, optional residual R of the output dtype; a_op = 1: W4 = [gate; up] = 2N rows and C[m,n] =
+ * silu(gate) * up with gate and up rounded to the output dtype first (vg_gemm_f8's SwiGLU), R must be NULL.  out_dtype VG_BF16 | VG_F32; no bias.
+ * Shapes: M > 16, K in {3072, 4096, 8192, 14336}, N a multiple of 8 (vg_gemm_w4a8_supported(N, K) != 0, launches nothing), VG_ERR_UNSUPPORTED otherwise.
+ * lda and ldw_bytes multiples of 16 that cover a row, A8 / W4 16-byte aligned, C / R rows 16-byte aligned: VG_ERR_ARG otherwise.  No workspace. */
+int vg_gemm_w4a8_supported(int64_t N, int64_t K);
+int vg_gemm_w4a8(const uint8_t* A8, int64_t lda, const float* a_scale, const uint8_t* W4, int64_t ldw_bytes, void* C, int64_t ldc,
+                 const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int out_dtype, int a_op, vg_stream_t stream);
 /* Which kernel an (M, N, K) GEMM of vg_gemm / vg_gemm_window is routed to with the current knobs (measurement aid:
  * bench.py attributes per-launch times to kernels with it): 0 gemm_skinny_kernel (M <= 16), 1 gemm_tile_glds_kernel,
  * 2 gemm_tile_k64b_kernel, 3 gemm_tile_w128_kernel, 4 gemm_tile_s128_kernel.  N = output columns (F for a_op == 1).

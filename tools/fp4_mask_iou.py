@@ -1,4 +1,5 @@
-"""Masks and logits of MXFP4 decode weights (cfg["llm"]["decode_weights"] = "mxfp4") against the bf16 path on the full-size synthetic C1 model
+"""Masks and logits of MXFP4 decode weights (cfg["llm"]["decode_weights"] = "mxfp4"), and of the MXFP4 prefill on top of them (prefill_gemm = "mxfp4"),
+against the bf16 path on the full-size synthetic C1 model
 (Llama-3-8B + towers + SAM2-L, random weights) — tools/fp8_mask_iou.py's clip and teacher forcing: the mxfp4 run is made to emit the ids of the bf16
 run, so both see the same sequence.  Prints, as DESIGN section 8 quotes them for fp8: relative error and cosine of the lm_head logits per step (formed
 here from the final-norm rows and the bf16 lm_head), argmax agreement on the free steps, cosine of the [SEG] embeddings, mask IoU mean / min.
@@ -51,18 +52,23 @@ def run(c):
     return out_ids[0].tolist(), logits, masks, cap
 
 
+def report(what, ids4, lg4, got, cap4):
+    assert ids4 == ids16
+    rel = (lg16 - lg4).norm(dim=1) / lg16.norm(dim=1)
+    cos = torch.nn.functional.cosine_similarity(lg16, lg4)
+    free = [i for i in range(len(emitted)) if i not in forced]
+    agree = sum(cap16["argmax"][i] == cap4["argmax"][i] for i in free) / max(len(free), 1)
+    ecos = torch.nn.functional.cosine_similarity(cap16["emb"], cap4["emb"]).min().item()
+    iou = np.array([[float((got[t, n] & ref[t, n]).sum() / max((got[t, n] | ref[t, n]).sum(), 1)) for n in range(ref.shape[1])] for t in range(T)])
+    print(f"{what} vs bf16 (synthetic weights, {ref.shape[1]} objects x {T} frames, {len(emitted)} steps): logits rel err per step max {rel.max():.3f} "
+          f"mean {rel.mean():.3f}, cosine min {cos.min():.4f}, argmax agreement {agree:.2f} of the {len(free)} free steps, [SEG] embedding cosine min {ecos:.4f}, "
+          f"mask IoU mean {iou.mean():.4f} min {iou.min():.4f}")
+    print("   per-mask [t][n]:", np.round(iou, 3).tolist())
+
+
 ids16, lg16, ref, cap16 = run(dict(cfg, forced_tokens=forced))
 emitted = ids16[ids.shape[1]:]
-c4 = dict(cfg, llm=dict(cfg["llm"], decode_weights="mxfp4"), forced_tokens={i: t for i, t in enumerate(emitted)})
-ids4, lg4, got, cap4 = run(c4)
-assert ids4 == ids16
-rel = (lg16 - lg4).norm(dim=1) / lg16.norm(dim=1)
-cos = torch.nn.functional.cosine_similarity(lg16, lg4)
-free = [i for i in range(len(emitted)) if i not in forced]
-agree = sum(cap16["argmax"][i] == cap4["argmax"][i] for i in free) / max(len(free), 1)
-ecos = torch.nn.functional.cosine_similarity(cap16["emb"], cap4["emb"]).min().item()
-iou = np.array([[float((got[t, n] & ref[t, n]).sum() / max((got[t, n] | ref[t, n]).sum(), 1)) for n in range(ref.shape[1])] for t in range(T)])
-print(f"mxfp4 decode weights vs bf16 (synthetic weights, {ref.shape[1]} objects x {T} frames, {len(emitted)} steps): logits rel err per step max {rel.max():.3f} "
-      f"mean {rel.mean():.3f}, cosine min {cos.min():.4f}, argmax agreement {agree:.2f} of the {len(free)} free steps, [SEG] embedding cosine min {ecos:.4f}, "
-      f"mask IoU mean {iou.mean():.4f} min {iou.min():.4f}")
-print("   per-mask [t][n]:", np.round(iou, 3).tolist())
+teacher = {i: t for i, t in enumerate(emitted)}
+report("mxfp4 decode weights", *run(dict(cfg, llm=dict(cfg["llm"], decode_weights="mxfp4"), forced_tokens=teacher)))
+# the third run: the prompt goes through the 4-bit MLP too (prefill_gemm = "mxfp4": e4m3 activations x the same packed rows; q|k|v and o on vg_gemm_f8)
+report("mxfp4 prefill + mxfp4 decode weights", *run(dict(cfg, llm=dict(cfg["llm"], decode_weights="mxfp4", prefill_gemm="mxfp4"), forced_tokens=teacher)))

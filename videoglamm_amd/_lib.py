@@ -28,6 +28,8 @@ def _sig(lib):
         "vg_gemm_splitk": ([P, L, P, L, P, L, P, P, P, L, I, I, I, I, I, I, I, P, L, P], c_int),
         "vg_quantize_fp8_rows": ([P, L, P, L, P, L, I, I, P], c_int),
         "vg_gemm_f8": ([P, L, P, P, L, P, P, L, P, P, L, L, L, L, I, I, P], c_int),
+        "vg_gemm_w4a8_supported": ([L, L], c_int),
+        "vg_gemm_w4a8": ([P, L, P, P, L, P, L, P, L, L, L, L, I, I, P], c_int),
         "vg_gemm_route": ([L, L, L, I, I, I], c_int),
         "vg_mlp_rows_supported": ([I, I], c_int),
         "vg_mlp_rows": ([P, L, P, L, P, P, F, P, P, P, P, L, I, I, I, P], c_int),

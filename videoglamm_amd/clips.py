@@ -129,6 +129,7 @@ def _group(params, cfg, towers, clips, g0, g1, max_new_tokens, eos_token_id, tok
     if dec is None or dec.max_len < need:
         dec = LlamaDecoder(params, cfg["llm"], decoder_len(need))
         params._decoder = dec          # the same cache (and captured decode graphs) generate() uses
+    dec.check_dense(cfg["llm"])
     rope_rows, cover = rows_cover(params, dec)
     if not batched_route(n, rope_rows, dw, dec.chain_roles, routes, os.environ, switch="VG_CLIPS_BATCHED", **cover):
         return _alone(*args)

@@ -124,7 +124,8 @@ class VideoGLaMMForCausalLM:
             if kwargs.get(k):
                 raise NotImplementedError(f"{k}: bitsandbytes quantisation (R/chat.py:247-272) is CUDA-only; the fp8 LLM path of this build is "
                                           "cfg['llm']['decode_weights'] = cfg['llm']['prefill_gemm'] = 'fp8', and the native 4-bit (MXFP4) decode "
-                                          "weights are cfg['llm']['decode_weights'] = 'mxfp4'")
+                                          "weights are cfg['llm']['decode_weights'] = 'mxfp4' (with cfg['llm']['prefill_gemm'] = 'mxfp4' and "
+                                          "cfg['llm']['dense_mlp'] = 'drop' the prefill runs on them too and the dense MLP weights are let go)")
         self.dtype = torch_dtype
         self.device = torch.device(device)
         if self.device.type == "cuda":
@@ -211,6 +212,10 @@ class VideoGLaMMForCausalLM:
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if (dtype, device) != (self.dtype, self.device):
+            if self.P.dropped:
+                raise RuntimeError("this model dropped its dense MLP weights (cfg['llm']['dense_mlp'] = 'drop'): the state dict no longer holds the "
+                                   f"tensors a copy in {dtype} on {device} would be built from; cast or move the model before its first inference, "
+                                   "or load the checkpoint again")
             self.dtype, self.device = dtype, device
             if device.type == "cuda":
                 torch.cuda.set_device(device)

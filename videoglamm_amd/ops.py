@@ -754,6 +754,33 @@ def decode_gemv_w4(x, w4, scales=None, norm_w=None, eps=0.0, residual=None, glu=
     return _decode_proj("vg_decode_gemv_w4", x, w4, (_p(scales),), norm_w, eps, residual, glu, out_dtype, out)
 
 
+def linear_w4a8_supported(N, K):
+    """True when the MXFP4 prefill GEMM covers a [N, K] weight (vg_gemm_w4a8_supported: K a packed row length, N a multiple of 8)."""
+    return bool(_lib.load().vg_gemm_w4a8_supported(int(N), int(K)))
+
+
+def linear_w4a8(q, qs, w4_packed, residual=None, glu=False, out_dtype=torch.bfloat16, out=None):
+    """e4m3 activations x MXFP4 weights (vg_gemm_w4a8): q uint8 [M,K] + qs [M] from quantize_fp8; w4_packed uint8 [N or 2N, 64 * SPL + K/2], the packed
+    rows of mxfp4_pack read in place (any row stride that is a multiple of 16).  glu: rows [gate; up], y = silu(gate) * up.  q may be row-strided;
+    out: a [M,N] destination of out_dtype (rows 16-byte aligned) instead of a new tensor."""
+    lib = _lib.load()
+    M, K = q.shape
+    N = w4_packed.shape[0] // 2 if glu else w4_packed.shape[0]
+    assert q.dtype == torch.uint8 and w4_packed.dtype == torch.uint8 and q.stride(1) == 1 and w4_packed.stride(1) == 1
+    assert qs.dtype == torch.float32 and qs.numel() == M and qs.is_contiguous()
+    assert K not in MXFP4_K or w4_packed.shape[1] == 64 * MXFP4_K[K] + K // 2, "packed MXFP4 rows of another row length"
+    y = torch.empty(M, N, dtype=out_dtype, device=q.device) if out is None else out
+    assert y.shape == (M, N) and y.dtype == out_dtype and y.stride(1) == 1
+    r2 = None
+    ldr = 0
+    if residual is not None:
+        r2, mr, ldr = _rows2d(residual)
+        assert r2.dtype == out_dtype and mr == M and r2.shape[1] == N
+    rc = lib.vg_gemm_w4a8(_p(q), q.stride(0), _p(qs), _p(w4_packed), w4_packed.stride(0), _p(y), y.stride(0), _p(r2), ldr, M, N, K, _dt(y), 1 if glu else 0, _stream())
+    _lib.check(rc, "vg_gemm_w4a8")
+    return y
+
+
 def decode_attention_workspace(H, Hkv, D, max_len, device):
     """zero-filled once: the workspace ends with per-KV-head arrival counters that the kernel resets itself."""
     n = _lib.load().vg_decode_attention_ws_floats(H, Hkv, D, max_len)

@@ -17,9 +17,31 @@ class Params:
         self.dtype = dtype
         self.kalign = 8 if dtype == torch.bfloat16 else 4
         self._c = {}
+        self.dropped = set()      # names whose dense weight drop() removed
+        self.ffn = None           # the LLM's MLP width, noted by the decoder that dropped the dense MLP weights (their shapes are gone with them)
 
     def has(self, name):
         return name in self.sd
+
+    def drop(self, names):
+        """Let go of the dense form of the named weights (cfg dense_mlp = "drop"): their source tensors leave self.sd and their model-dtype copies —
+        w(), fused() and t() entries — leave the cache; quantised forms already built from them (fp4(), fp8()) stay.  Names that are not in the
+        state dict are ignored (Llama stores gate and up, Phi-3 the fused gate_up_proj).  A later dense access raises a KeyError that says so."""
+        names = set(names)
+        for n in names:
+            if self.sd.pop(n + ".weight", None) is not None or n in self.dropped:
+                self.dropped.add(n)
+            self.sd.pop(n + ".bias", None)
+        for key in list(self._c):
+            kind, rest = key[0], key[1:]
+            if (kind in ("w", "fused") and any(r in names for r in rest)) or (kind == "t" and rest[0].rsplit(".", 1)[0] in names):
+                del self._c[key]
+
+    def _dense(self, name):
+        """the source tensor of a dense weight, or the KeyError of a dropped one"""
+        if name in self.dropped:
+            raise KeyError(f"{name}: the dense weight was dropped (cfg dense_mlp = 'drop' keeps the packed MXFP4 rows only)")
+        return self.sd[name + ".weight"]
 
     def _get(self, key, fn):
         if key not in self._c:
@@ -36,7 +58,7 @@ class Params:
     # ---- dense
     def w(self, name):
         """nn.Linear / 1x1 conv weight -> [N, Kpad] in the model dtype."""
-        return self._get(("w", name), lambda: self._padk(self.sd[name + ".weight"].reshape(self.sd[name + ".weight"].shape[0], -1)))
+        return self._get(("w", name), lambda: self._padk(self._dense(name).reshape(self._dense(name).shape[0], -1)))
 
     def f32(self, name):
         """bias / norm weight / LayerScale vector -> fp32 contiguous (None when absent)."""
@@ -55,11 +77,11 @@ class Params:
     def fused(self, names, stored=None):
         """row-concatenation of several [N_i, K] weights (qkv, gate|up) -> ([sum N_i, Kpad], fp32 bias or None).
         stored: name of a checkpoint tensor that already IS that concatenation (Phi-3's qkv_proj / gate_up_proj)."""
-        if stored is not None and stored + ".weight" in self.sd:
+        if stored is not None and (stored + ".weight" in self.sd or stored in self.dropped):
             return self.w(stored), self.b(stored)
 
         def make():
-            w = torch.cat([self.sd[n + ".weight"] for n in names], dim=0)
+            w = torch.cat([self._dense(n) for n in names], dim=0)
             bs = [self.sd.get(n + ".bias") for n in names]
             bias = None
             if any(x is not None for x in bs):
@@ -73,7 +95,7 @@ class Params:
     def fp8(self, names, stored=None):
         """fused()/w() of the named weights quantised for the decode GEMVs: (uint8 [N,K] OCP-e4m3 codes, fp32 [N] row scales).
         Made once from the packed model-dtype weight (so the bf16 prefill and the fp8 decode see the same rounding of the
-        checkpoint first); kept beside it — the prefill GEMMs stay bf16."""
+        checkpoint first) and kept beside it; also the operands of the fp8 prefill (cfg prefill_gemm = "fp8", and q|k|v / o under "mxfp4")."""
         from . import ops
 
         names = [names] if isinstance(names, str) else list(names)
@@ -86,7 +108,8 @@ class Params:
     def fp4(self, names, stored=None):
         """fused()/w() of the named weights as MXFP4 for the decode GEMVs (cfg decode_weights = "mxfp4"): the packed rows of ops.mxfp4_pack
         (uint8 [N, scale head + K/2]: e2m1 codes, one e8m0 scale per 32 K elements).  Made once from the packed model-dtype weight and kept beside
-        it, as fp8(); the prefill GEMMs stay in the model dtype."""
+        it, as fp8().  The same rows are the MLP operand of the prefill under cfg prefill_gemm = "mxfp4" (vg_gemm_w4a8), and under dense_mlp =
+        "drop" they are all that is kept: drop() removes the dense weight they were made from."""
         from . import ops
 
         names = [names] if isinstance(names, str) else list(names)

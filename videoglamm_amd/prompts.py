@@ -99,6 +99,7 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
     if dec is None or dec.max_len < need:
         dec = LlamaDecoder(params, cfg["llm"], -(-need // 1024) * 1024)
         params._decoder = dec          # the same cache (and captured decode graphs) generate() uses
+    dec.check_dense(cfg["llm"])
     dec.reset()
     dec.forward(prefix)                # K/V and final-norm rows [0, P): shared by every prompt
     stage_mark(stages, "prefill")
@@ -162,17 +163,13 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
 
 def rows_cover(params, dec):
     """(rope_rows, dict(attn_rows, w8_rows, w4_rows)): which forms of the B-row step cover this decoder — batched_route's shape arguments"""
-    rope_rows = dec.rope_path and ops.decode_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype)
+    rope_rows = dec.rope_path and ops.decode_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, dec.ffn, params.dtype)
     attn_rows = (not dec.rope_path and dec.fused_decode and params.device.type == "cuda"
-                 and ops.decode_step_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, _ffn(params), params.dtype))
+                 and ops.decode_step_rows_supported(dec.H, dec.Hkv, dec.hd, dec.D, dec.ffn, params.dtype))
     # fp8 / mxfp4 decode weights: every quantised weight of the step (dec.proj: gate|up, down, the lm_head) has a B-row kernel of its shape
     quant = all(dec.proj.covered(N, K, fmt) for N, K, fmt, _ in dec.proj.weights(quantised=True))
     w8_rows, w4_rows = dec.w8 and quant, dec.w4 and quant
     return rope_rows, dict(attn_rows=attn_rows, w8_rows=w8_rows, w4_rows=w4_rows)
-
-
-def _ffn(params):
-    return params.t("model.layers.0.mlp.down_proj.weight").shape[1]
 
 
 def decode_rows(rows, out, max_new_tokens, eos, token_hook=None, traces=None):

@@ -204,6 +204,32 @@ def decode_gemv_mode(value, decode_weights, dtype, env, step, projections, suppo
     return "mfma_q"
 
 
+def prefill_gemm_mode(value, decode_weights, dense_mlp, dtype, hidden, ffn):
+    """cfg["llm"]["prefill_gemm"] and cfg["llm"]["dense_mlp"] -> (mode, drop).  mode: "mxfp4" (the MLP of the prefill on the packed MXFP4 rows the
+    decode step streams: vg_gemm_w4a8 on the tile path, vg_decode_gemv_w4_rows for short prefills; q|k|v and o on vg_gemm_f8), "fp8"
+    (every GEMM of the tile path on vg_gemm_f8) or None — any other value keeps the dense GEMMs of the model dtype.  drop: dense_mlp = "drop",
+    the decoder builds the packed rows of every layer and lets go of the dense gate / up / down weights (Params.drop); valid only when neither the
+    prefill nor the decode step would read them, a ValueError names the reader otherwise.  decode_weights: cfg["llm"]["decode_weights"]; dtype: the
+    model's; hidden, ffn: the MLP's widths.  Pure: no device work."""
+    if dense_mlp not in (None, "keep", "drop"):
+        raise ValueError(f"cfg['llm']['dense_mlp'] = {dense_mlp!r}: 'keep' (default) or 'drop'")
+    drop = dense_mlp == "drop"
+    if value != "mxfp4":
+        if drop:
+            raise ValueError(f"dense_mlp = 'drop': the prefill (prefill_gemm = {value!r}) still reads the dense MLP weights; "
+                             "it needs prefill_gemm = 'mxfp4' and decode_weights = 'mxfp4'")
+        return ("fp8" if value == "fp8" else None), False
+    if dtype != torch.bfloat16:
+        raise ValueError(f"prefill_gemm = 'mxfp4' needs a bf16 model (e4m3 activations x MXFP4 weights with bf16 rows between the GEMMs), not {dtype}")
+    if hidden not in (3072, 4096, 8192) or ffn not in (8192, 14336):
+        raise ValueError(f"prefill_gemm = 'mxfp4': no packed MXFP4 row of length hidden = {hidden} / ffn = {ffn} "
+                         "(hidden 3072, 4096 or 8192 and ffn 8192 or 14336)")
+    if drop and decode_weights != "mxfp4":
+        raise ValueError(f"dense_mlp = 'drop': the decode step (decode_weights = {decode_weights!r}) still reads the dense MLP weights; "
+                         "it needs prefill_gemm = 'mxfp4' and decode_weights = 'mxfp4'")
+    return "mxfp4", drop
+
+
 def kv_cache_mode(value, dtype, device_type, fused, env):
     """cfg["llm"]["kv_cache"] -> truthy when the decode step keeps its keys / values as e4m3 codes: True for "fp8" (the
     decode_attention form of the step at every width), the string "rope" for "fp8_rope" (the same format on the rope step: Llama-3 width);
@@ -395,7 +421,9 @@ class LlamaDecoder:
         self.kpw, self.kpw_min = 0, int(os.environ.get("VG_DEC_KPW_MIN", "2048"))
         self.attn_ws = None
         es = 2 if dt == torch.bfloat16 else 4
-        ffn = c.get("ffn") or params.t("model.layers.0.mlp.down_proj.weight").shape[1]
+        # (params.ffn: the width an earlier decoder on these Params noted when it dropped the dense MLP weights, dense_mlp = "drop")
+        ffn = c.get("ffn") or params.ffn or params.t("model.layers.0.mlp.down_proj.weight").shape[1]
+        self.ffn = ffn
         # the fused decode kernels' shape limits (vg_decode_gemv / vg_decode_attention); VG_DECODE_FUSED=0 = A/B knob
         # fp8 (e4m3) weights with per-row scales in the decode step's MLP GEMVs and the lm_head (cfg["decode_weights"] == "fp8": the decode
         # side of BASELINE config C4's "fp8 LLM path"; bf16 activations, fp32 accumulation; the prefill GEMMs stay bf16)
@@ -404,7 +432,12 @@ class LlamaDecoder:
         # takes the fp8 GEMV (it decides the token ids and is 4 % of the remaining bytes), the attention projections stay bf16 as under "fp8"
         self.w4 = c.get("decode_weights") == "mxfp4"
         # fp8 MFMA prefill GEMMs (cfg["prefill_gemm"] == "fp8"): vg_quantize_fp8_rows + vg_gemm_f8; the attention itself stays bf16
-        self.f8_prefill = c.get("prefill_gemm") == "fp8"
+        # cfg["prefill_gemm"] == "mxfp4": the MLP of the prefill on the packed MXFP4 rows (vg_gemm_w4a8; q|k|v and o as under "fp8"), and
+        # cfg["dense_mlp"] == "drop": no dense gate / up / down weights are kept (prefill_gemm_mode; the packed rows are built at the end of __init__)
+        pmode, self.dense_dropped = prefill_gemm_mode(c.get("prefill_gemm"), c.get("decode_weights"), c.get("dense_mlp"), dt, self.D, ffn)
+        self.w4_prefill = pmode == "mxfp4"
+        self.check_dense(c)
+        self.f8_prefill = pmode == "fp8"
         assert not self.f8_prefill or dt == torch.bfloat16, "the fp8 prefill pairs with a bf16 model"
         if self.w8:
             assert dt == torch.bfloat16 and self.D in (3072, 4096, 8192) and ffn in (8192, 14336), "fp8 decode weights: bf16 model, supported row lengths"
@@ -460,6 +493,28 @@ class LlamaDecoder:
         # sampled decoding (vg_sample): None = greedy; else dict(T, k, p, seed), the values held in the device block samp_params that
         # the captured step reads — a new temperature / top-p / top-k / seed is a copy into it, never a re-capture
         self.sampling, self.samp_params, self.samp_ws, self.samp_fast = None, None, None, False
+        if self.dense_dropped:
+            self._drop_dense_mlp()
+
+    def check_dense(self, c):
+        """RuntimeError when the dense MLP weights of these Params are gone (dense_mlp = "drop") and cfg c asks for a mode that reads them"""
+        if self.P.dropped and (c.get("prefill_gemm") != "mxfp4" or c.get("decode_weights") != "mxfp4"):
+            reader = f"the prefill (prefill_gemm = {c.get('prefill_gemm')!r})" if c.get("prefill_gemm") != "mxfp4" else \
+                f"the decode step (decode_weights = {c.get('decode_weights')!r})"
+            raise RuntimeError(f"the dense MLP weights of this model were dropped (dense_mlp = 'drop'): {reader} would read them; "
+                               "keep prefill_gemm = decode_weights = 'mxfp4' or load the checkpoint again")
+
+    def _drop_dense_mlp(self):
+        """dense_mlp = "drop": layer by layer, the packed MXFP4 rows, then the layer's dense gate / up / down tensors leave the state dict and the
+        cache — at no moment does more than one layer hold its concatenated gate|up copy and the quantiser's temporaries beside the packed rows"""
+        P = self.P
+        P.ffn = self.ffn
+        for i in range(self.c["num_layers"]):
+            l = f"model.layers.{i}."
+            gu = [l + "mlp.gate_proj", l + "mlp.up_proj"]
+            P.fp4(gu, stored=l + "mlp.gate_up_proj")
+            P.fp4(l + "mlp.down_proj")
+            P.drop(gu + [l + "mlp.gate_up_proj", l + "mlp.down_proj"])
 
     def reset(self):
         self.pos = 0
@@ -489,7 +544,8 @@ class LlamaDecoder:
         all-gathers the other ranks' rows there)."""
         P, c = self.P, self.c
         S = x.shape[0]
-        f8 = self.f8_prefill and S > 16 and pos_dev is None
+        w4 = self.w4_prefill        # (the mode is fixed at construction, as every mode of the decoder is)
+        f8 = (self.f8_prefill or w4) and S > 16 and pos_dev is None
         for i in range(c["num_layers"]):
             l = f"model.layers.{i}."
             qkv_names = [l + "self_attn.q_proj", l + "self_attn.k_proj", l + "self_attn.v_proj"]
@@ -513,11 +569,24 @@ class LlamaDecoder:
             if f8:
                 x = ops.linear_f8(*ops.quantize_fp8(o.view(S, self.D)), *P.fp8(l + "self_attn.o_proj"), residual=x)
                 h = ops.rmsnorm(x, P.f32(l + "post_attention_layernorm.weight"), c["rms_eps"])
+                if w4:      # MXFP4 prefill: e4m3 activations x the packed rows the decode step streams (vg_gemm_w4a8)
+                    a = ops.linear_w4a8(*ops.quantize_fp8(h), P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), glu=True)
+                    x = ops.linear_w4a8(*ops.quantize_fp8(a), P.fp4(l + "mlp.down_proj"), residual=x)
+                    continue
                 a = ops.linear_f8(*ops.quantize_fp8(h), *P.fp8(gu_names, stored=l + "mlp.gate_up_proj"), glu=True)
                 x = ops.linear_f8(*ops.quantize_fp8(a), *P.fp8(l + "mlp.down_proj"), residual=x)
                 continue
             x = ops.linear(o.view(S, self.D), P.w(l + "self_attn.o_proj"), residual=x)
             h = ops.rmsnorm(x, P.f32(l + "post_attention_layernorm.weight"), c["rms_eps"])
+            if w4:
+                # MXFP4 prefill off the tile path (S <= 16, or a device-side position): the MLP on the decode step's B-row GEMV, 16 rows at a time
+                wgu4, wd4 = P.fp4(gu_names, stored=l + "mlp.gate_up_proj"), P.fp4(l + "mlp.down_proj")
+                y = torch.empty_like(x)
+                for r in range(0, S, 16):
+                    a = ops.decode_gemv_w4_rows(h[r:r + 16], wgu4, glu=True)
+                    ops.decode_gemv_w4_rows(a, wd4, residual=x[r:r + 16], out=y[r:r + 16])
+                x = y
+                continue
             wgu, _ = P.fused(gu_names, stored=l + "mlp.gate_up_proj")
             # gate|up in one GEMM; for the decode step the SwiGLU runs in that GEMV's epilogue (ops.linear(glu=True))
             x = ops.linear(ops.linear(h, wgu, glu=True), P.w(l + "mlp.down_proj"), residual=x)
@@ -577,6 +646,7 @@ class LlamaDecoder:
         """eager: x [S,D] new tokens appended at self.pos -> final-normed hidden [S,D] (also kept in hid_all)."""
         S, pos = x.shape[0], self.pos
         assert pos + S <= self.max_len
+        self.check_dense(self.c)        # (the decoder's own cfg dict edited in place after a drop)
         if self.kv8 and pos > self.staged:
             # rows [staged, pos) came from decode steps, which append to the e4m3 cache only: the staging takes what that cache holds
             for i in range(self.c["num_layers"]):
@@ -902,6 +972,7 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     if dec is None or dec.max_len < need:
         dec = LlamaDecoder(params, cfg["llm"], -(-need // 1024) * 1024)
         params._decoder = dec          # KV cache + captured decode graph are reused across clips
+    dec.check_dense(cfg["llm"])        # (a kept decoder does not follow the live cfg; after dense_mlp = "drop" a cfg that asks for a dense mode is refused, not ignored)
     dec.reset()
     dec.set_sampling(sampling)
     if comm is not None and comm.world > 1 and x.shape[0] >= 64 * comm.world and os.environ.get("VG_PREFILL_SHARDED", "0") == "1":

@@ -27,8 +27,10 @@ Covered — pytest cases per entry point (139 in all; a case loops over its shap
   ops.linear_rows ............. 8 (K, N) without LayerNorm / RoPE: plain, ReLU, residual, A + A2, block-strided A
 GLU forms: SiLU has no exact form, so they are compared bit for bit with ops.swiglu of the SAME kernel's non-GLU output over the 2N rows, which the
 exact test has just pinned (one vg_silu definition serves every site).
-Left out, because their arithmetic has no exact form: vg_gemm_ln, vg_mlp_rows, the LayerNorm / RoPE forms of vg_gemm_rows, vg_twoway_image_update,
-vg_mask_upscale, the quantisers, and GELU / SiLU / sigmoid epilogues (they stay with the tolerance tests of test_kernels_gpu.py).
+Left out, because their arithmetic has no exact form: vg_gemm_ln, vg_mlp_rows, the LayerNorm / RoPE forms of vg_gemm_rows, the quantisers, and GELU /
+SiLU / sigmoid epilogues (they stay with the tolerance tests of test_kernels_gpu.py and the rounding-level tests of test_rowwise_accuracy_gpu.py).
+vg_twoway_image_update and vg_mask_upscale are in tests/test_decoder_fused_gpu.py: a selector design under which the two-way update's contractions
+ARE exact, and float64 chains that round where the kernels round.
 
 Wall time on one MI355X: 22 s for the 139 cases (the three child processes 2.3 - 2.7 s each, every other case under 1 s)."""
 import os

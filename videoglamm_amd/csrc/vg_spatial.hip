@@ -525,9 +525,15 @@ extern "C" int vg_bilinear_mask(const float* in, uint8_t* out, int N, int Hi, in
   VG_CHECK((Wo & 3) || (((uintptr_t)out) & 3) == 0, VG_ERR_ARG, "vg_bilinear_mask: out must be 4-byte aligned");
   if (N == 0) return VG_OK;
   const int64_t groups = (int64_t)N * ((Ho + BM_ROWS - 1) / BM_ROWS);
-  if (Wi <= BM_MAXW && groups < (1ll << 31))
+  if (Wi <= BM_MAXW && groups < (1ll << 31)) {
+    // at Wi = BM_MAXW the rows take 64 KB and the 32 static bytes of wy come on top: past the default limit of a launch, so the limit is raised
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute((const void*)bilinear_mask_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BM_ROWS * BM_MAXW * (int)sizeof(float));
+      attr = true;
+    }
     bilinear_mask_rows_kernel<<<(unsigned)groups, 256, (size_t)2 * BM_ROWS * Wi * sizeof(float), (hipStream_t)stream>>>(in, out, N, Hi, Wi, Ho, Wo);
-  else
+  } else
     bilinear_mask_kernel<<<sp_grid((int64_t)N * Ho * ((Wo + 3) / 4)), 256, 0, (hipStream_t)stream>>>(in, out, N, Hi, Wi, Ho, Wo);
   VG_LAUNCH_CHECK();
   return VG_OK;

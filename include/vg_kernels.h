@@ -658,6 +658,19 @@ int vg_mask_pair_counts(const uint8_t* a, const uint8_t* b, int64_t* inter, int6
  * R/eval_referdavis_metrics.py:194-259.  fg, gt: uint8 [N,H,W]. */
 int vg_boundary_counts(const uint8_t* fg, const uint8_t* gt, int64_t* out, int N, int H, int W, int radius,
                        vg_stream_t stream);
+/* out[n] = {xmin, ymin, xmax, ymax, area} (int32 [N,5]) of mask n of mask:[N,H,W] uint8 (foreground = nonzero); the
+ * maxima are INCLUSIVE pixel indices, an empty mask gives {W, H, -1, -1, 0}.  The integer part of masks_to_boxes,
+ * R/utils/grounding_utils/box_ops.py:118-142.  All N masks in one call; out is fully written by the call (no memset
+ * by the caller, no dependence on its previous contents); mask needs no alignment.  Integer min / max / sum: the
+ * result does not depend on the order of the reduction.  H * W < 2^31, N <= 65535. */
+int vg_mask_boxes(const uint8_t* mask, int32_t* out, int N, int H, int W, vg_stream_t stream);
+/* The same table for the mask AFTER vg_remove_small_blobs(min_size) (4-connectivity, components of fewer than
+ * min_size pixels cleared), without writing that mask and reading it back: bit for bit
+ * vg_mask_boxes(vg_remove_small_blobs(mask, min_size)) — R/eval_grounding.py:281-287.  out_mask: NULL, or uint8
+ * [N,H,W] that receives exactly what vg_remove_small_blobs writes.  ws_labels / ws_counts: int32 [N,H,W] scratch.
+ * min_size <= 0 is VG_ERR_ARG (vg_mask_boxes is the unfiltered reduction). */
+int vg_blob_boxes(const uint8_t* mask, int32_t* out, uint8_t* out_mask, int32_t* ws_labels, int32_t* ws_counts, int N,
+                  int H, int W, int min_size, vg_stream_t stream);
 
 /* ---- small MLP heads (r06) ----
  * vg_mlp3_grouped: G independent three-layer MLPs (Linear, ReLU, Linear, ReLU, Linear; sigmoid on the outputs of head g when bit g of sig_mask is set)

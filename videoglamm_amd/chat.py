@@ -8,6 +8,7 @@ The container has no decord / cv2, so a "video" is a directory of frame images (
 """
 import argparse
 import glob
+import json
 import os
 
 import numpy as np
@@ -37,6 +38,8 @@ def get_args():
     p.add_argument("--max_new_tokens", type=int, default=1024)     # R/chat.py:566
     p.add_argument("--seed", type=int, default=None, help="torch.manual_seed(N) before the first clip: reproducible sampled decoding")
     p.add_argument("--greedy", action="store_true", help="decode greedily even when the checkpoint's generation_config sets do_sample")
+    p.add_argument("--save_boxes", action="store_true", help="also write boxes.json (frame -> object -> x_min, y_min, x_max, y_max of the mask) "
+                                                              "next to caption.txt; the boxes are reduced on the device")
     return p.parse_args()
 
 
@@ -118,6 +121,12 @@ def load_image(path):
     return [[np.array(Image.open(path).convert("RGB"))]]
 
 
+def write_boxes(boxes, save_dir):
+    """boxes.json: frame -> object -> [x_min, y_min, x_max, y_max] (inference(return_boxes=True): inclusive maxima, [1e8, 1e8, 0, 0] = empty)"""
+    with open(os.path.join(save_dir, "boxes.json"), "w") as fh:
+        json.dump({str(t): {str(k): [float(v) for v in b] for k, b in fr.items()} for t, fr in boxes.items()}, fh)
+
+
 def main():
     args = get_args()
     if args.base_model_type.split("|")[0] != "vgpt":
@@ -144,10 +153,11 @@ def main():
             precision=args.precision)
         prompt = args.prompt_text or input("Please input your prompt: ")
         input_ids = conv_generator.apply_for_chat(prompt, type=kind, tokenizer=tokenizer)
-        output_ids, video_segments = model.inference(images=enc_image, context_images=enc_context_image, images_for_sam=image_sam,
-                                                     input_ids=input_ids, resize_list=resize_list, original_size_list=original_size_list,
-                                                     max_new_tokens=args.max_new_tokens,
-                                                     use_sam2_video_branch=args.use_sam2_video_branch)
+        extra = {"return_boxes": True} if args.save_boxes else {}
+        output_ids, video_segments, *video_boxes = model.inference(images=enc_image, context_images=enc_context_image, images_for_sam=image_sam,
+                                                                   input_ids=input_ids, resize_list=resize_list,
+                                                                   original_size_list=original_size_list, max_new_tokens=args.max_new_tokens,
+                                                                   use_sam2_video_branch=args.use_sam2_video_branch, **extra)
         text = host.decode_text(output_ids, tokenizer)
         print("text_output: ", text)
         save_dir = os.path.join(args.vis_save_path, os.path.basename(path.rstrip("/")).split(".")[0])
@@ -155,6 +165,8 @@ def main():
         host.write_masks(video_segments[0], np.stack(np_images[0]), save_dir)
         with open(os.path.join(save_dir, "caption.txt"), "w") as fh:       # R/chat.py:594-596
             fh.write(text)
+        if args.save_boxes:
+            write_boxes(video_boxes[0][0], save_dir)
         if args.prompt_text and args.video:
             break
 

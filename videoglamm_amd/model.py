@@ -144,6 +144,10 @@ class VideoGLaMMForCausalLM:
         # what the reference's evaluation does on the host afterwards (remove_small_blobs(min_size=20),
         # R/eval_gcg_infer.py:20-29,182).  0 = the reference's inference() behaviour.
         self.min_blob_size = int(kwargs.get("min_blob_size", 0))
+        # this call's return_boxes (set by the inference surface, read by _binarize / _download); _fused: the (masks, box table) pair
+        # of a _binarize that filtered the blobs and reduced the boxes in one chain
+        self._want_boxes = False
+        self._fused = None
         # diagnostics only: when set to a dict, inference() leaves the fp32 mask logits ("logits", device), the [SEG] embeddings
         # ("emb") and the model's own per-step argmaxes ("argmax") in it (bench.py's self-check, tests)
         self.capture = None
@@ -286,18 +290,26 @@ class VideoGLaMMForCausalLM:
 
     # ------------------------------------------------------------------ inference surface
     def inference(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                  max_new_tokens=32, use_sam2_video_branch=False, **sampling):
+                  max_new_tokens=32, use_sam2_video_branch=False, *, return_boxes=False, **sampling):
         """R/model/VideoGLaMM.py:560-596.  Keyword-only extras: do_sample / temperature / top_k / top_p (override model.generation_config for
-        this call) and generator (the torch.Generator the sampling seed is drawn from)."""
+        this call), generator (the torch.Generator the sampling seed is drawn from) and return_boxes: a third return value
+        [{frame: {obj: np.float32[4]}}] with the keys of the masks' dictionaries, the postproc.masks_to_boxes value (x_min, y_min, x_max, y_max;
+        [1e8, 1e8, 0, 0] for an empty mask) of exactly the mask that is returned, reduced on the device before the masks are downloaded."""
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             torch.cuda.set_device(self.device)
         if use_sam2_video_branch:
             if self.config.use_sam2:
                 return self.inference_video_branch(images, context_images, images_for_sam, input_ids, resize_list,
-                                                   original_size_list, max_new_tokens, **sampling)
+                                                   original_size_list, max_new_tokens, return_boxes=return_boxes, **sampling)
             raise ValueError("use_sam2_video_branch is True, but model is not configured to use SAM2")
         return self.inference_framewise(images, context_images, images_for_sam, input_ids, resize_list,
-                                        original_size_list, max_new_tokens, **sampling)
+                                        original_size_list, max_new_tokens, return_boxes=return_boxes, **sampling)
+
+    def _set_return_boxes(self, return_boxes):
+        if return_boxes and self.comm is not None:
+            raise NotImplementedError("return_boxes runs on one GPU: the masks of a multi-GPU model are sharded over the ranks; "
+                                      "use postproc.masks_to_boxes on the returned masks")
+        self._want_boxes, self._fused = bool(return_boxes), None
 
     def _resolve_sampling(self, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
         """this call's decoding mode; multi-GPU: every rank adopts rank 0's seed (the decode is replicated and must emit the same ids)"""
@@ -350,6 +362,10 @@ class VideoGLaMMForCausalLM:
     def _binarize(self, logits):
         """[T,N,H,W] fp32 logits -> uint8 masks (logit > 0), small blobs removed when min_blob_size is set."""
         masks = ops.threshold(logits)
+        if self._want_boxes and self.min_blob_size > 0:      # blob filter and boxes from one union-find (vg_blob_boxes)
+            table, masks = ops.mask_boxes(masks, self.min_blob_size, return_mask=True)
+            self._fused = (masks, table)
+            return masks
         return ops.remove_small_blobs(masks, self.min_blob_size) if self.min_blob_size > 0 else masks
 
     @staticmethod
@@ -376,6 +392,26 @@ class VideoGLaMMForCausalLM:
         torch.cuda.current_stream(masks.device).synchronize()
         return out
 
+    def _download(self, masks):
+        """device uint8 masks [T,N,H,W] -> (host masks, None) or, under return_boxes, (host masks, float32 ndarray [T,N,4]): the boxes of all
+        T x N masks from ONE ops.mask_boxes call on the device masks, enqueued before the download (16 bytes per mask cross PCIe on top of the masks)."""
+        if not self._want_boxes:
+            return self._to_host(masks), None
+        from .postproc import boxes_xyxy
+        fused, self._fused = self._fused, None
+        table = fused[1] if fused is not None and fused[0] is masks else ops.mask_boxes(masks)
+        boxes = boxes_xyxy(table)
+        return self._to_host(masks), boxes.cpu().numpy()
+
+    def _result(self, host, boxes):
+        """the tail of an inference()'s return value: ([segments],) or, under return_boxes, ([segments], [boxes]) with the same keys"""
+        if host is None:            # no [SEG]
+            return ([{}], [{}]) if self._want_boxes else ([{}],)
+        segs = self._segments(host)
+        if not self._want_boxes:
+            return ([segs],)
+        return [segs], [{t: {k: boxes[i, j] for j, k in enumerate(fr)} for i, (t, fr) in enumerate(segs.items())}]
+
     def _hiera_async(self, sam, frames=None, all_frames=False, bufs=None):
         """Hiera + FPN of the SAM frames on a side HIP stream.  It depends only on the pixels, not on the LLM, and it is
         MFMA/LDS-bound while the LLM decode loop is an HBM-bound GEMV chain: the two overlap on the chip.  Returns
@@ -400,14 +436,16 @@ class VideoGLaMMForCausalLM:
         return feats, join
 
     def inference_framewise(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                            max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None, empty_ok=False):
+                            max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None, empty_ok=False,
+                            return_boxes=False):
         """R/model/VideoGLaMM.py:598-768 -> (output_ids [1,L+G], [ {frame: {obj: mask}} ]).  empty_ok: no [SEG] gives [{}] as the video branch
-        does, not the reference's exception (inference_prompts' meaning of such a prompt)."""
+        does, not the reference's exception (inference_prompts' meaning of such a prompt).  return_boxes: see inference()."""
+        self._set_return_boxes(return_boxes)
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens)
         if emb.shape[0] == 0 and empty_ok:
-            return out_ids, [{}]
+            return (out_ids,) + self._result(None, None)
         if emb.shape[0] == 0:
             # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
             raise AttributeError("'tuple' object has no attribute 'shape'")
@@ -419,18 +457,20 @@ class VideoGLaMMForCausalLM:
             stage_mark(self.stages, "mask_decode")
             return out_ids, [self._segments(host, frame_ids=fids)]
         elif self._fast_masks():
-            masks = self._to_host(self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=True)[0])
+            masks, boxes = self._download(self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=True)[0])
             stage_mark(self.stages, "mask_decode")
         else:
             logits, _ = self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats)
             if self.capture is not None:
                 self.capture["logits"] = logits
-            masks = self._to_host(self._binarize(logits))
-        return out_ids, [self._segments(masks)]
+            masks, boxes = self._download(self._binarize(logits))
+        return (out_ids,) + self._result(masks, boxes)
 
     def inference_video_branch(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                               max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
-        """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842)."""
+                               max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None,
+                               return_boxes=False):
+        """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842).  return_boxes: see inference()."""
+        self._set_return_boxes(return_boxes)
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         # multi-GPU: frames shard for Hiera only (the propagation is a recurrence over frames) and every rank needs every frame's features:
@@ -440,7 +480,7 @@ class VideoGLaMMForCausalLM:
         graphed = self.comm is None and self.device.type == "cuda" and os.environ.get("VG_VIDEO_GRAPH", "1") == "1"
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens, all_frames=streamed, static_feats=graphed)
         if emb.shape[0] == 0:
-            return out_ids, [{}]
+            return (out_ids,) + self._result(None, None)
         hw = tuple(original_size_list[0])
         if self.comm is not None:
             # OBJECTS shard for the propagation
@@ -458,25 +498,26 @@ class VideoGLaMMForCausalLM:
             fast = self._fast_masks()
             out = self.sam2.video_branch_graphed(sam, emb, hw, feats, as_masks=fast)
             if fast:
-                host = self._to_host(out)
+                host, boxes = self._download(out)
                 stage_mark(self.stages, "propagation")
-                return out_ids, [self._segments(host)]
+                return (out_ids,) + self._result(host, boxes)
             logits = out
         elif self._fast_masks():
-            host = self._to_host(self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=True))
+            host, boxes = self._download(self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=True))
             stage_mark(self.stages, "propagation")
-            return out_ids, [self._segments(host)]
+            return (out_ids,) + self._result(host, boxes)
         else:
             logits = self.sam2.video_branch(sam, emb, hw, frame_feats=feats)
         if self.capture is not None:
             self.capture["logits"] = logits
-        return out_ids, [self._segments(self._to_host(self._binarize(logits)))]
+        return (out_ids,) + self._result(*self._download(self._binarize(logits)))
 
     # ------------------------------------------------------------------ several prompts about one clip
     def inference_prompts(self, images, context_images, images_for_sam, input_ids_list, resize_list, original_size_list,
                           max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                          generator=None, shared=None):
+                          generator=None, shared=None, return_boxes=False):
         """B prompts ([1, L_b] or [L_b] each) about ONE clip -> (output ids [1, L_b + G_b] per prompt, {frame: {obj: mask}} per prompt).
+        return_boxes adds a third list, {frame: {obj: np.float32[4]}} per prompt (see inference(); {} where the masks are {}).
         Entry b means what inference(..., input_ids=input_ids_list[b]) means; a prompt without a [SEG] gets {} (as the video branch does,
         R/model/VideoGLaMM.py:840-842).  The towers, Hiera and the prefill of the shared prefix (system text + visual block, identical ids in
         every prompt) run once; SAM2 runs once with every prompt's [SEG] embeddings as its objects.  Sampling draws one seed per prompt from
@@ -488,6 +529,7 @@ class VideoGLaMMForCausalLM:
         from .prompts import GROUP, check_prompts
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_prompts() runs on one GPU: call inference() per prompt on a multi-GPU model")
+        self._set_return_boxes(return_boxes)
         ids_list = [torch.as_tensor(x).cpu().long() for x in input_ids_list]
         if not ids_list:
             raise NotImplementedError("inference_prompts() needs at least one prompt")
@@ -507,33 +549,35 @@ class VideoGLaMMForCausalLM:
         if not shared:
             return self._prompts_alone(images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens,
                                        use_sam2_video_branch, dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                                                   generator=generator))
+                                                                   generator=generator, return_boxes=self._want_boxes))
         samplings = [resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator) for _ in ids_list]
-        out_ids, segs = [], []
+        out_ids, segs, boxes = [], [], []
         for g in range(0, len(ids_list), GROUP):
-            o, s = self._prompts_group(images, context_images, images_for_sam, ids_list[g:g + GROUP], original_size_list, max_new_tokens,
-                                       use_sam2_video_branch, samplings[g:g + GROUP])
+            o, s, b = self._prompts_group(images, context_images, images_for_sam, ids_list[g:g + GROUP], original_size_list, max_new_tokens,
+                                          use_sam2_video_branch, samplings[g:g + GROUP])
             out_ids += o
             segs += s
-        return out_ids, segs
+            boxes += b
+        return (out_ids, segs, boxes) if self._want_boxes else (out_ids, segs)
 
     def _prompts_alone(self, images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens, video, sampling):
         """inference_prompts() as one inference() per prompt, in list order (each call draws its own sampling seed from the generator); the
         captures of the calls are gathered per prompt as _prompts_group leaves them."""
-        out_ids, segs, caps = [], [], []
+        out_ids, segs, boxes, caps = [], [], [], []
         keep = self.capture
         try:
             for ids in ids_list:
                 if keep is not None:
                     self.capture = {}
                 if video:
-                    o, s = self.inference_video_branch(images, context_images, images_for_sam, ids[None], resize_list, original_size_list,
-                                                       max_new_tokens, **sampling)
+                    o, s, *b = self.inference_video_branch(images, context_images, images_for_sam, ids[None], resize_list, original_size_list,
+                                                           max_new_tokens, **sampling)
                 else:
-                    o, s = self.inference_framewise(images, context_images, images_for_sam, ids[None], resize_list, original_size_list,
-                                                    max_new_tokens, empty_ok=True, **sampling)
+                    o, s, *b = self.inference_framewise(images, context_images, images_for_sam, ids[None], resize_list, original_size_list,
+                                                        max_new_tokens, empty_ok=True, **sampling)
                 out_ids.append(o)
                 segs.append(s[0])
+                boxes += [x[0] for x in b]
                 caps.append(self.capture)
         finally:
             self.capture = keep
@@ -541,7 +585,7 @@ class VideoGLaMMForCausalLM:
             for k in ("argmax", "emb", "logits"):
                 if any(k in c for c in caps):
                     keep[k] = [c.get(k) for c in caps]
-        return out_ids, segs
+        return (out_ids, segs, boxes) if sampling["return_boxes"] else (out_ids, segs)
 
     def _prompts_group(self, images, context_images, images_for_sam, ids_list, original_size_list, max_new_tokens, video, samplings):
         from .prompts import generate_prompts
@@ -578,7 +622,7 @@ class VideoGLaMMForCausalLM:
             self.capture["argmax"] = [t.get("argmax", []) for t in traces]
             self.capture["emb"] = [emb[a:a + n] for a, n in zip(starts, counts)]
         if emb.shape[0] == 0:
-            return out, [{} for _ in ids_list]
+            return out, [{} for _ in ids_list], [{} for _ in ids_list]
         hw = tuple(original_size_list[0])
         fast = self._fast_masks()
         if video:
@@ -592,15 +636,18 @@ class VideoGLaMMForCausalLM:
             if self.capture is not None:
                 self.capture["logits"] = [res[:, a:a + n] for a, n in zip(starts, counts)]
             res = self._binarize(res)
-        host = self._to_host(res)
+        host, boxes = self._download(res)
         stage_mark(self.stages, "propagation" if video else "mask_decode")
-        # objects [a, a + n) are prompt b's, renumbered from 0
-        return out, [self._segments(host[:, a:a + n]) if n else {} for a, n in zip(starts, counts)]
+        # objects [a, a + n) are prompt b's, renumbered from 0 (the third list stays empty without return_boxes)
+        per = [self._result(host[:, a:a + n], None if boxes is None else boxes[:, a:a + n]) if n else self._result(None, None)
+               for a, n in zip(starts, counts)]
+        return out, [p[0][0] for p in per], [p[1][0] for p in per if self._want_boxes]
 
     # ------------------------------------------------------------------ several clips, one prompt each
     def inference_clips(self, clips, max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                        generator=None):
-        """B clips, one prompt each -> a list whose entry b is what inference(*clips[b], max_new_tokens, use_sam2_video_branch, ...) returns:
+                        generator=None, return_boxes=False):
+        """B clips, one prompt each -> a list whose entry b is what inference(*clips[b], max_new_tokens, use_sam2_video_branch, ...) returns
+        (with return_boxes: inference()'s third element, [{frame: {obj: np.float32[4]}}], in every clip's tuple):
         (output ids [1, L_b + G_b], [{frame: {obj: mask}}]), the same ids and the same masks pixel for pixel.  clips[b]: the six per-clip arguments
         of inference() (images, context_images, images_for_sam, input_ids, resize_list, original_size_list) as a tuple or a dict.
         Every clip runs its own towers, Hiera and whole-prompt prefill; the clips of a group (up to 16) then decode together, one row per clip in
@@ -611,6 +658,7 @@ class VideoGLaMMForCausalLM:
         from .clips import as_clip, groups
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_clips() runs on one GPU: call inference() per clip on a multi-GPU model")
+        self._set_return_boxes(return_boxes)
         clips = [as_clip(c, b) for b, c in enumerate(clips)]
         if not clips:
             raise NotImplementedError("inference_clips() needs at least one clip")
@@ -657,14 +705,14 @@ class VideoGLaMMForCausalLM:
         out = []
         for b, ((out_ids, emb), clip) in enumerate(zip(res, clips)):
             joins[b]()
-            out.append((out_ids.unsqueeze(0), self._clip_masks(sams.pop(b), emb, feats.pop(b), tuple(clip[5][0]), video)))
+            out.append((out_ids.unsqueeze(0),) + self._clip_masks(sams.pop(b), emb, feats.pop(b), tuple(clip[5][0]), video))
         return out
 
     def _clip_masks(self, sam, emb, feats, hw, video):
-        """the single-GPU mask decode of inference_video_branch / inference_framewise for one clip (capture unset)"""
+        """the single-GPU mask decode of inference_video_branch / inference_framewise for one clip (capture unset): _result's tuple"""
         if emb.shape[0] == 0:
             if video:
-                return [{}]
+                return self._result(None, None)
             # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
             raise AttributeError("'tuple' object has no attribute 'shape'")
         fast = self._fast_masks()
@@ -675,4 +723,4 @@ class VideoGLaMMForCausalLM:
                 res = self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=fast)
         else:
             res = self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=fast)[0]
-        return [self._segments(self._to_host(res if fast else self._binarize(res)))]
+        return self._result(*self._download(res if fast else self._binarize(res)))

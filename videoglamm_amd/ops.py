@@ -1734,6 +1734,24 @@ def boundary_counts(fg, gt, radius):
     return out
 
 
+def mask_boxes(masks, min_size=0, return_mask=False):
+    """masks [..., H, W] bool/uint8 -> int32 [..., 5] = (xmin, ymin, xmax, ymax, area) per mask, maxima inclusive,
+    (W, H, -1, -1, 0) for an empty mask.  min_size > 0: the table of the mask after remove_small_blobs(min_size), from
+    the union-find's own finalize pass; return_mask adds that filtered uint8 mask (the input itself at min_size 0)."""
+    lib = _lib.load()
+    m = _u8(masks)
+    H, W = m.shape[-2:]
+    N = m.numel() // (H * W)
+    out = torch.empty(tuple(m.shape[:-2]) + (5,), dtype=torch.int32, device=m.device)
+    if min_size <= 0:
+        _lib.check(lib.vg_mask_boxes(_p(m), _p(out), N, H, W, _stream()), "vg_mask_boxes")
+        return (out, m) if return_mask else out
+    ws = torch.empty((2,) + tuple(m.shape), dtype=torch.int32, device=m.device)
+    kept = torch.empty_like(m) if return_mask else None
+    _lib.check(lib.vg_blob_boxes(_p(m), _p(out), _p(kept), _p(ws[0]), _p(ws[1]), N, H, W, int(min_size), _stream()), "vg_blob_boxes")
+    return (out, kept) if return_mask else out
+
+
 # ---------------------------------------------------------------- image pre-processing on the device (§8f-1)
 def resample_u8(x, out_size, axis, bounds, coeffs):
     """one pass of Pillow's 8-bit resampler over x [N,H,W,C] uint8; bounds [out,2] / coeffs [out,ksize] int32 on device."""

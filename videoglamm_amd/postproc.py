@@ -11,6 +11,10 @@ pairing of compute_miou, the F formula) is the reference's float64 host arithmet
   compute_iou / compute_miou   R/eval_gcg_metrics.py:26-60
   db_eval_iou                  R/eval_referdavis_metrics.py:147-176   (void_pixels is not supported)
   db_eval_boundary / f_measure R/eval_referdavis_metrics.py:178-259
+  masks_to_boxes               R/utils/grounding_utils/box_ops.py:118-142   (min_size: this build's extension)
+  np_box_area / np_box_iou     R/utils/grounding_utils/box_ops.py:12-62     (the reference's numpy arithmetic, on the host)
+  calc_tiou                    R/eval_grounding.py:55-72                    (_calc_tiou)
+  video_grounding_metrics      R/eval_grounding.py:326-405                  (the per-video record of the VidSTG / HC-STVG driver)
 """
 import numpy as np
 import torch
@@ -126,3 +130,94 @@ def db_eval_boundary(annotation, segmentation, void_pixels=None, bound_th=0.008)
 
 def f_measure(foreground_mask, gt_mask, void_pixels=None, bound_th=0.008):
     return db_eval_boundary(gt_mask, foreground_mask, void_pixels, bound_th)
+
+
+# ---------------------------------------------------------------- grounding evaluation (VidSTG / HC-STVG): boxes, tIoU, vIoU
+def boxes_xyxy(table):
+    """int32 [..., 5] of ops.mask_boxes -> float32 [..., 4] as the reference's masks_to_boxes gives it: inclusive maxima,
+    [1e8, 1e8, 0, 0] for an empty mask (its masked_fill value under min, and the max of an all-zero product)."""
+    empty = table[..., 4:5] == 0
+    fill = torch.tensor([1e8, 1e8, 0.0, 0.0], dtype=torch.float32, device=table.device)
+    return torch.where(empty, fill, table[..., :4].to(torch.float32))
+
+
+def masks_to_boxes(masks, min_size=0):
+    """[N, H, W] masks -> float32 device tensor [N, 4] = (x_min, y_min, x_max, y_max), zeros((0, 4)) for no pixels at all.
+    The reduction runs where the masks are (ops.mask_boxes): 20 bytes per mask leave the device, and only when the caller
+    asks for host values.  min_size > 0 gives the boxes of remove_small_blobs(mask, min_size) in the same chain."""
+    m = _mask(masks)
+    if m.numel() == 0:
+        return torch.zeros((0, 4), dtype=torch.float32, device=m.device)
+    return boxes_xyxy(ops.mask_boxes(m, min_size))
+
+
+def np_box_area(boxes):
+    assert boxes.ndim == 2 and boxes.shape[-1] == 4
+    return (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
+
+
+def _box_inter_union(boxes1, boxes2):
+    area1, area2 = np_box_area(boxes1), np_box_area(boxes2)
+    lt = np.maximum(boxes1[:, None, :2], boxes2[:, :2])
+    rb = np.minimum(boxes1[:, None, 2:], boxes2[:, 2:])
+    wh = (rb - lt).clip(min=0)
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    return inter, area1[:, None] + area2 - inter
+
+
+def np_box_iou(boxes1, boxes2):
+    """[N, 4] x [M, 4] (x1, y1, x2, y2) -> [N, M]; numpy's own dtype promotion and division (a degenerate pair divides by 0)."""
+    inter, union = _box_inter_union(boxes1, boxes2)
+    return inter / union
+
+
+def calc_tiou(gt_sted, pred_sted, frame_ids):
+    """(tiou, frames of the union span, set of frames of the intersection span); spans are [start, end)."""
+    max_start, min_end = max(gt_sted[0], pred_sted[0]), min(gt_sted[1], pred_sted[1])
+    min_start, max_end = min(gt_sted[0], pred_sted[0]), max(gt_sted[1], pred_sted[1])
+    if min_end <= max_start:
+        tiou = 0
+    else:
+        intersection = min_end - max_start
+        tiou = intersection / ((gt_sted[1] - gt_sted[0]) + (pred_sted[1] - pred_sted[0]) - intersection)
+    union_predgt = [f for f in frame_ids if min_start <= f < max_end]
+    inter_predgt = set(f for f in frame_ids if max_start <= f < min_end)
+    return tiou, union_predgt, inter_predgt
+
+
+def _box14(b):
+    if torch.is_tensor(b):
+        b = b.detach().cpu().numpy()
+    return np.asarray(b).reshape(1, 4)
+
+
+def video_grounding_metrics(pred_boxes, gt_boxes, gt_sted, frame_ids, pred_sted=None, iou_thresholds=(0.3, 0.5)):
+    """The per-video record of R/eval_grounding.py:326-405.  pred_boxes / gt_boxes: {frame: box [4] or [1, 4]}; gt_sted: the
+    annotated moment, both ends INCLUSIVE here (the driver iterates range(gt_sted[0], gt_sted[1] + 1)); pred_sted: the predicted
+    span when the model localises in time (the driver's tmp_loc), which adds tiou / viou / viou@thr.
+    ONE box per frame: the driver overwrites predictions[t] in its loop over the objects of a frame (:281-287), so it scores the
+    LAST object's box; which object to score is the caller's choice here.
+    A frame of the annotated moment without a prediction raises RuntimeError, as the driver does."""
+    rec = {"img_metrics": {}}
+    if pred_sted is not None:
+        tiou, union_predgt, inter_predgt = calc_tiou(gt_sted, pred_sted, frame_ids)
+        rec.update(gt_sted=gt_sted, pred_sted=pred_sted, tiou=tiou)
+    inter_frames = list(range(gt_sted[0], gt_sted[1] + 1))
+    viou = gt_viou = 0
+    for f in inter_frames:
+        if f not in pred_boxes:
+            raise RuntimeError(f"No prediction for frame {f}")
+        pb, gb = _box14(pred_boxes[f]), _box14(gt_boxes[f])
+        iou = np_box_iou(pb, gb)[0][0]
+        rec["img_metrics"][f] = {"iou": iou, "pred_box": pb[0], "gt_box": gb[0]}
+        if pred_sted is not None and f in inter_predgt:
+            viou += iou
+        gt_viou += iou
+    if pred_sted is not None:
+        viou = viou / max(len(union_predgt), 1)
+        rec["viou"] = viou
+        rec.update({f"viou@{t}": int(viou > t) for t in iou_thresholds})
+    gt_viou = gt_viou / max(len(inter_frames), 1)
+    rec["gt_viou"] = gt_viou
+    rec.update({f"gt_viou@{t}": int(gt_viou > t) for t in iou_thresholds})
+    return rec

@@ -671,6 +671,34 @@ int vg_mask_boxes(const uint8_t* mask, int32_t* out, int N, int H, int W, vg_str
  * min_size <= 0 is VG_ERR_ARG (vg_mask_boxes is the unfiltered reduction). */
 int vg_blob_boxes(const uint8_t* mask, int32_t* out, uint8_t* out_mask, int32_t* ws_labels, int32_t* ws_counts, int N,
                   int H, int W, int min_size, vg_stream_t stream);
+/* COCO's uncompressed run-length code of every mask of mask:[N,H,W] uint8 (foreground = nonzero), in the form of
+ * mask_to_rle_pytorch (R/model/segment_anything_2/sam2/utils/amg.py:109-137): the pixels in COLUMN-major order
+ * j = x * H + y; P = the ascending j >= 1 whose foreground bit differs from that of j - 1 (across column ends too); the
+ * counts are the differences of [0] + P + [H * W], with a single 0 in front when pixel 0 is foreground.  An empty mask is
+ * [H * W], a full one [0, H * W].  Two phases, so that the caller allocates the output exactly:
+ *   vg_mask_rle_count  n_runs[n] (int32 [N]) = len(P) + 1 + fg(pixel 0), and ws_cols (int32 [N, 4, U] scratch, fully
+ *                      rewritten by every call; U = vg_mask_rle_units(H, W) = W * ceil(H / R) column segments of
+ *                      R = max(64, ceil(H / 65535)) rows) = what the second phase needs per column segment: its write
+ *                      offset (the exclusive scan of the segments' transition counts in the code's order), the last
+ *                      transition at or before its end (a max-scan), its first / last pixel and whether its first pixel
+ *                      opens a run.
+ *   vg_mask_rle_emit   offsets: int64 [N + 1], the exclusive sum of n_runs, made by the caller; counts: int32
+ *                      [offsets[N]].  Mask n's counts go to counts[offsets[n] : offsets[n + 1]], all of them and nothing
+ *                      else; every store index is clamped to that range.  mask and ws_cols as the first phase left them.
+ * Each phase reads the mask once, in dwords along the rows (a lane owns 4 adjacent columns and walks down them); stream
+ * order is the only dependency between the launches.  mask needs no alignment.  H * W < 2^31, 4 * U < 2^31 (it bites
+ * only for masks of at most 64 rows and W >= 2^29), N <= 65535; vg_rle_to_mask refuses the same shapes. */
+int vg_mask_rle_units(int H, int W); /* U of ws_cols; 0 for a shape the entry points refuse.  Launches nothing. */
+int vg_mask_rle_count(const uint8_t* mask, int32_t* ws_cols, int32_t* n_runs, int N, int H, int W, vg_stream_t stream);
+int vg_mask_rle_emit(const uint8_t* mask, const int32_t* ws_cols, const int64_t* offsets, int32_t* counts, int N, int H,
+                     int W, vg_stream_t stream);
+/* The inverse (rle_to_mask, amg.py:140-151): out:[N,H,W] uint8 0 / 1, row-major, from counts (int32, flat) and offsets
+ * (int64 [N + 1], nondecreasing, offsets[N] <= the length of counts: they are read, and trusted).  ws_ends: int32 scratch
+ * of the length of counts (the per-mask inclusive scan).  status[n] (int32 [N]) = 1 and mask n all zero when a count of
+ * code n is negative or its counts do not sum to exactly H * W; other masks are unaffected.  Zero counts inside a code are
+ * legal.  Gather form: every output pixel looks its run up, so no count value takes part in a store address. */
+int vg_rle_to_mask(const int32_t* counts, const int64_t* offsets, uint8_t* out, int32_t* status, int32_t* ws_ends, int N,
+                   int H, int W, vg_stream_t stream);
 
 /* ---- small MLP heads (r06) ----
  * vg_mlp3_grouped: G independent three-layer MLPs (Linear, ReLU, Linear, ReLU, Linear; sigmoid on the outputs of head g when bit g of sig_mask is set)

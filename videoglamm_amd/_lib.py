@@ -137,6 +137,10 @@ def _sig(lib):
         "vg_boundary_counts": ([P, P, P, I, I, I, I, P], c_int),
         "vg_mask_boxes": ([P, P, I, I, I, P], c_int),
         "vg_blob_boxes": ([P, P, P, P, P, I, I, I, I, P], c_int),
+        "vg_mask_rle_units": ([I, I], c_int),
+        "vg_mask_rle_count": ([P, P, P, I, I, I, P], c_int),
+        "vg_mask_rle_emit": ([P, P, P, P, I, I, I, P], c_int),
+        "vg_rle_to_mask": ([P, P, P, P, P, I, I, I, P], c_int),
         "vg_resample_u8": ([P, P, I, I, I, I, I, I, P, P, I, P], c_int),
         "vg_resize_cv_linear_u8": ([P, P, I, I, I, I, I, I, P, P, P, P, P], c_int),
         "vg_normalize_u8": ([P, P, I, I, I, I, I, I, I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), I, I, P], c_int),

@@ -40,6 +40,8 @@ def get_args():
     p.add_argument("--greedy", action="store_true", help="decode greedily even when the checkpoint's generation_config sets do_sample")
     p.add_argument("--save_boxes", action="store_true", help="also write boxes.json (frame -> object -> x_min, y_min, x_max, y_max of the mask) "
                                                               "next to caption.txt; the boxes are reduced on the device")
+    p.add_argument("--save_rle", action="store_true", help="also write rle.json (frame -> object -> COCO RLE with a compressed counts string) "
+                                                            "next to caption.txt; the masks are encoded on the device")
     return p.parse_args()
 
 
@@ -127,6 +129,13 @@ def write_boxes(boxes, save_dir):
         json.dump({str(t): {str(k): [float(v) for v in b] for k, b in fr.items()} for t, fr in boxes.items()}, fh)
 
 
+def write_rle(codes, save_dir):
+    """rle.json: frame -> object -> {"size": [h, w], "counts": str} (inference(return_rle=True), compressed as pycocotools writes it)"""
+    from .postproc import coco_encode_rle
+    with open(os.path.join(save_dir, "rle.json"), "w") as fh:
+        json.dump({str(t): {str(k): coco_encode_rle(c) for k, c in fr.items()} for t, fr in codes.items()}, fh)
+
+
 def main():
     args = get_args()
     if args.base_model_type.split("|")[0] != "vgpt":
@@ -153,8 +162,8 @@ def main():
             precision=args.precision)
         prompt = args.prompt_text or input("Please input your prompt: ")
         input_ids = conv_generator.apply_for_chat(prompt, type=kind, tokenizer=tokenizer)
-        extra = {"return_boxes": True} if args.save_boxes else {}
-        output_ids, video_segments, *video_boxes = model.inference(images=enc_image, context_images=enc_context_image, images_for_sam=image_sam,
+        extra = {k: True for k, on in (("return_boxes", args.save_boxes), ("return_rle", args.save_rle)) if on}
+        output_ids, video_segments, *video_extra = model.inference(images=enc_image, context_images=enc_context_image, images_for_sam=image_sam,
                                                                    input_ids=input_ids, resize_list=resize_list,
                                                                    original_size_list=original_size_list, max_new_tokens=args.max_new_tokens,
                                                                    use_sam2_video_branch=args.use_sam2_video_branch, **extra)
@@ -166,7 +175,9 @@ def main():
         with open(os.path.join(save_dir, "caption.txt"), "w") as fh:       # R/chat.py:594-596
             fh.write(text)
         if args.save_boxes:
-            write_boxes(video_boxes[0][0], save_dir)
+            write_boxes(video_extra[0][0], save_dir)
+        if args.save_rle:
+            write_rle(video_extra[-1][0], save_dir)
         if args.prompt_text and args.video:
             break
 

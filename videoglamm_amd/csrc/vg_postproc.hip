@@ -19,6 +19,9 @@
 //                          (masks_to_boxes, R/utils/grounding_utils/box_ops.py:118-142), and blob_boxes: the same table
 //                          for the mask after remove_small_blobs, reduced on the finalize side of the union-find
 //                          (the chain of R/eval_grounding.py:281-287).
+//   mask_rle / rle_to_mask : COCO's uncompressed run-length code of every mask of a batch, in two phases (count, emit),
+//                          and its inverse in gather form (mask_to_rle_pytorch / rle_to_mask,
+//                          R/model/segment_anything_2/sam2/utils/amg.py:109-151).
 #include "vg_common.h"
 
 namespace {
@@ -572,6 +575,264 @@ int box_init(int32_t* out, int N, int H, int W, hipStream_t st) {
   return VG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- run-length codes
+// COCO's uncompressed RLE in the form of mask_to_rle_pytorch (R/model/segment_anything_2/sam2/utils/amg.py:109-137): the
+// pixels of a mask in COLUMN-major order j = x * H + y, a count for every run, a leading 0 when pixel 0 is foreground.
+// The mask is row-major, so a lane owns RLE_G adjacent columns (one dword of every row) and walks down the rows: a wave
+// reads 256 contiguous bytes per row, and a column's state (previous bit, count / write index, last transition) stays in
+// registers.  A column is cut into S = ceil(H / R) segments of R rows (rle_rows) so that a 1024-row mask is walked by 16
+// lanes per column group and not by one; segment s of column x is unit u = x * S + s, and the units in this order cover
+// the pixels in the code's order.  Unit u owns the transitions at its own pixels: those inside it and the one at its
+// first pixel against the pixel before it, which is the LAST pixel of unit u - 1 (the row above, or, for s = 0, the
+// last pixel of column x - 1: the comparison runs across column ends).
+//
+// ws_cols: int32 [N, 4, U], U = W * S.  After rle_count_kernel: [0] transitions inside the unit, [1] the position j of
+// the last of them (-1: none), [2] bit 0 = first pixel, bit 1 = last pixel.  rle_scan_kernel (one workgroup per mask,
+// its own launch: nothing waits on another workgroup) turns [0] into the exclusive scan of the units' transition counts
+// (the unit's write offset), [1] into the inclusive max-scan "last transition at or before this unit's end" (0: none;
+// unit u starts its first run at [1][u - 1] without seeing another unit's pixels), and writes [3] = 1 where the unit's
+// first pixel differs from the one before it.  Every entry is rewritten by every call: no state survives.
+constexpr int RLE_G = 4;
+
+// rows per column segment: 64, more only where the grid's y extent (65535) asks for it
+inline int rle_rows(int H) { return max(64, (H + 65534) / 65535); }
+
+// the foreground bits of w <= RLE_G adjacent pixels of a row (bit k = pixel k).  FULL: one dword load at whatever
+// alignment the row has (gfx950 takes unaligned global dwords; hipcc emits global_load_dword for it); otherwise the
+// last lane group of a row whose W is no multiple of RLE_G, byte by byte and never past the row's end.
+template <bool FULL>
+__device__ __forceinline__ uint32_t rle_row_bits(const uint8_t* row, int w) {
+  uint32_t v = 0;
+  if (FULL) {
+    __builtin_memcpy(&v, row, 4);
+  } else {
+    for (int k = 0; k < w; ++k) v |= (uint32_t)row[k] << (8 * k);
+  }
+  const uint32_t z = nz_bytes(v) >> 7;
+  return (z | (z >> 7) | (z >> 14) | (z >> 21)) & 15u;
+}
+
+// f(y, bits) for the rows y0 + 1 .. y1 - 1 of the lane's columns, in order (p: the lane's first column in row 0)
+template <class F>
+__device__ __forceinline__ void rle_walk(const uint8_t* p, int y0, int y1, int W, int w, F&& f) {
+  if (w == RLE_G) {
+#pragma unroll 8
+    for (int y = y0 + 1; y < y1; ++y) f(y, rle_row_bits<true>(p + (int64_t)y * W, w));
+  } else {
+    for (int y = y0 + 1; y < y1; ++y) f(y, rle_row_bits<false>(p + (int64_t)y * W, w));
+  }
+}
+
+// grid (lane groups of 64, S, N)
+__global__ __launch_bounds__(64) void rle_count_kernel(const uint8_t* __restrict__ mask, int32_t* __restrict__ ws, int H, int W, int R) {
+  const int n = blockIdx.z, seg = blockIdx.y, S = gridDim.y, x0 = (blockIdx.x * 64 + threadIdx.x) * RLE_G;
+  if (x0 >= W) return;
+  const int w = min(RLE_G, W - x0), y0 = seg * R, y1 = min(H, y0 + R), U = W * S;
+  const uint8_t* p = mask + (int64_t)n * H * W + x0;
+  int32_t* c = ws + (int64_t)n * 4 * U;
+  const uint32_t first = w == RLE_G ? rle_row_bits<true>(p + (int64_t)y0 * W, w) : rle_row_bits<false>(p + (int64_t)y0 * W, w);
+  uint32_t prev = first;
+  int cnt[RLE_G], last[RLE_G];
+#pragma unroll
+  for (int k = 0; k < RLE_G; ++k) { cnt[k] = 0; last[k] = -1; }
+  rle_walk(p, y0, y1, W, w, [&](int y, uint32_t b) {
+    const uint32_t d = b ^ prev;
+    prev = b;
+#pragma unroll
+    for (int k = 0; k < RLE_G; ++k)
+      if ((d >> k) & 1) { ++cnt[k]; last[k] = y; }
+  });
+#pragma unroll
+  for (int k = 0; k < RLE_G; ++k) {
+    if (k >= w) break;
+    const int x = x0 + k, u = x * S + seg;
+    c[u] = cnt[k];
+    c[U + u] = last[k] < 0 ? -1 : x * H + last[k];
+    c[2 * U + u] = (int)(((first >> k) & 1) | (((prev >> k) & 1) << 1));
+  }
+}
+
+// inclusive scans over the 1024 values of a workgroup: sum and max at once.  wsum / wmax: 16 words of LDS each.
+__device__ __forceinline__ void rle_block_scan(int& s, int& m, int& total_s, int& total_m, int* wsum, int* wmax) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int a = __shfl_up(s, o, 64), b = __shfl_up(m, o, 64);
+    if (lane >= o) { s += a; m = max(m, b); }
+  }
+  if (lane == 63) { wsum[wave] = s; wmax[wave] = m; }
+  __syncthreads();
+  total_s = 0; total_m = 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    if (v < wave) { s += wsum[v]; m = max(m, wmax[v]); }
+    total_s += wsum[v]; total_m = max(total_m, wmax[v]);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(1024) void rle_scan_kernel(int32_t* ws, int32_t* n_runs, int H, int W, int S, int R) {
+  __shared__ int wsum[16], wmax[16];
+  const int n = blockIdx.x, t = threadIdx.x, U = W * S;
+  int32_t* c = ws + (int64_t)n * 4 * U;
+  int carry_s = 0, carry_m = 0;
+  for (int base = 0; base < U; base += 1024) {
+    const int u = base + t;
+    int own = 0, m = 0;
+    if (u < U) {
+      const int flag = u > 0 && (c[2 * U + u] & 1) != ((c[2 * U + u - 1] >> 1) & 1);
+      const int lp = c[U + u];
+      own = c[u] + flag;
+      m = lp >= 0 ? lp : (flag ? (u / S) * H + (u % S) * R : 0);       // the unit's first pixel
+      c[3 * U + u] = flag;
+    }
+    int s = own, ts, tm;
+    rle_block_scan(s, m, ts, tm, wsum, wmax);
+    if (u < U) {
+      c[u] = carry_s + s - own;
+      c[U + u] = max(carry_m, m);
+    }
+    carry_s += ts;
+    carry_m = max(carry_m, tm);
+  }
+  if (t == 0) n_runs[n] = carry_s + 1 + (c[2 * U] & 1);
+}
+
+__global__ __launch_bounds__(64) void rle_emit_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ ws,
+                                                      const int64_t* __restrict__ offsets, int32_t* __restrict__ counts, int H, int W, int R) {
+  const int n = blockIdx.z, seg = blockIdx.y, S = gridDim.y, x0 = (blockIdx.x * 64 + threadIdx.x) * RLE_G;
+  if (x0 >= W) return;
+  const int64_t lo = offsets[n], hi = offsets[n + 1];
+  if (hi <= lo) return;
+  const int w = min(RLE_G, W - x0), len = (int)min(hi - lo, (int64_t)0x7fffffff);
+  const int y0 = seg * R, y1 = min(H, y0 + R), U = W * S;
+  const uint8_t* p = mask + (int64_t)n * H * W + x0;
+  const int32_t* c = ws + (int64_t)n * 4 * U;
+  int32_t* out = counts + lo;
+  // every store goes through here: an index is clamped to the mask's own [offsets[n], offsets[n + 1])
+  auto put = [&](int i, int v) { out[min(max(i, 0), len - 1)] = v; };
+  const int fg0 = c[2 * U] & 1;
+  int idx[RLE_G], prev[RLE_G], xh[RLE_G];
+#pragma unroll
+  for (int k = 0; k < RLE_G; ++k) {
+    const int x = min(x0 + k, W - 1), u = x * S + seg;      // k >= w: a copy of the last column that never sees a transition (its bits are 0)
+    xh[k] = x * H;
+    idx[k] = fg0 + c[u];
+    prev[k] = u > 0 ? c[U + u - 1] : 0;
+    if (k < w && c[3 * U + u]) {              // the transition at the unit's first pixel
+      put(idx[k]++, xh[k] + y0 - prev[k]);
+      prev[k] = xh[k] + y0;
+    }
+  }
+  uint32_t pb = w == RLE_G ? rle_row_bits<true>(p + (int64_t)y0 * W, w) : rle_row_bits<false>(p + (int64_t)y0 * W, w);
+  rle_walk(p, y0, y1, W, w, [&](int y, uint32_t b) {
+    const uint32_t d = b ^ pb;
+    pb = b;
+#pragma unroll
+    for (int k = 0; k < RLE_G; ++k)
+      if ((d >> k) & 1) {
+        const int j = xh[k] + y;
+        put(idx[k]++, j - prev[k]);
+        prev[k] = j;
+      }
+  });
+  if (x0 == 0 && seg == 0 && fg0) put(0, 0);
+  if (x0 + w == W && seg == S - 1) {          // the run that ends the code
+    int last = prev[0];
+#pragma unroll
+    for (int k = 1; k < RLE_G; ++k) last = k < w ? prev[k] : last;
+    put(len - 1, H * W - last);
+  }
+}
+
+// decode, first launch: ends = the inclusive scan of mask n's counts (clamped to H * W: a larger value only occurs in a
+// code that is refused), status[n] = 1 when a count is negative or the total is not H * W.  One workgroup per mask.
+__global__ __launch_bounds__(256) void rle_ends_kernel(const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                                                       int32_t* __restrict__ ends, int32_t* __restrict__ status, int HW) {
+  __shared__ long long wsum[4];
+  const int n = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t lo = offsets[n], len = offsets[n + 1] - lo;
+  long long carry = 0;
+  int bad = 0;
+  for (int64_t base = 0; base < len; base += 256) {
+    const int64_t i = base + t;
+    long long s = 0;
+    if (i < len) {
+      const int v = counts[lo + i];
+      bad |= v < 0;
+      s = v < 0 ? 0 : v;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long a = __shfl_up(s, o, 64);
+      if (lane >= o) s += a;
+    }
+    if (lane == 63) wsum[wave] = s;
+    __syncthreads();
+    long long total = 0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      if (v < wave) s += wsum[v];
+      total += wsum[v];
+    }
+    __syncthreads();
+    if (i < len) ends[lo + i] = (int32_t)min(carry + s, (long long)HW);
+    carry += total;
+  }
+  bad = __syncthreads_or(bad);
+  if (t == 0) status[n] = (bad || carry != HW) ? 1 : 0;
+}
+
+// decode, second launch, in gather form: a lane owns RLE_G adjacent columns of a band of `rows` rows and asks, for each
+// of its pixels j = x * H + y, for the first run whose end lies beyond j (zero counts are skipped by that rule); the
+// run's parity is the pixel.  One binary search per column segment, then the index only advances.  The store address
+// is a function of the thread's index alone; a refused code (status[n] != 0) stores zeros.
+__global__ __launch_bounds__(64) void rle_gather_kernel(const int32_t* __restrict__ ends, const int64_t* __restrict__ offsets,
+                                                        const int32_t* __restrict__ status, uint8_t* __restrict__ out, int H, int W, int rows) {
+  const int n = blockIdx.z, x0 = (blockIdx.x * 64 + threadIdx.x) * RLE_G;
+  if (x0 >= W) return;
+  const int w = min(RLE_G, W - x0), y0 = blockIdx.y * rows, y1 = min(H, y0 + rows);
+  const int64_t lo = offsets[n];
+  const int len = (int)min(offsets[n + 1] - lo, (int64_t)0x7fffffff);
+  const bool ok = status[n] == 0 && len > 0;
+  const int32_t* e = ends + lo;
+  uint8_t* o = out + (int64_t)n * H * W + x0;
+  int idx[RLE_G], xh[RLE_G];
+#pragma unroll
+  for (int k = 0; k < RLE_G; ++k) {
+    xh[k] = min(x0 + k, W - 1) * H;
+    idx[k] = 0;
+    if (ok && k < w) {                        // upper bound of j0 in e[0, len - 1): e[len - 1] = H * W lies beyond every pixel
+      const int j0 = xh[k] + y0;
+      int a = 0, b = len - 1;
+      while (a < b) {
+        const int mid = a + ((b - a) >> 1);
+        if (e[mid] > j0) b = mid; else a = mid + 1;
+      }
+      idx[k] = a;
+    }
+  }
+  for (int y = y0; y < y1; ++y) {
+    uint32_t v = 0;
+    if (ok) {
+#pragma unroll
+      for (int k = 0; k < RLE_G; ++k) {
+        if (k < w) {
+          const int j = xh[k] + y;
+          while (idx[k] < len - 1 && e[idx[k]] <= j) ++idx[k];
+          v |= (uint32_t)(idx[k] & 1) << (8 * k);
+        }
+      }
+    }
+    uint8_t* q = o + (int64_t)y * W;
+    if (w == RLE_G) {
+      __builtin_memcpy(q, &v, 4);
+    } else {
+      for (int k = 0; k < w; ++k) q[k] = (uint8_t)(v >> (8 * k));
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int vg_connected_components(const uint8_t* mask, int32_t* labels, int32_t* counts, int N, int H, int W,
@@ -668,6 +929,57 @@ extern "C" int vg_boundary_counts(const uint8_t* fg, const uint8_t* gt, int64_t*
     return VG_ERR_LAUNCH;
   }
   boundary_counts_kernel<<<dim3((W + 63) / 64, (H + 63) / 64, N), 256, 0, st>>>(fg, gt, (unsigned long long*)out, H, W, radius);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+// U of ws_cols; 0 for a shape that is refused.  The kernels index the four planes of a mask's scratch in int (up to
+// 4 * U), so 4 * U < 2^31 belongs to the contract: it only bites for masks of at most 64 rows and W >= 2^29.
+extern "C" int vg_mask_rle_units(int H, int W) {
+  if (H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31)) return 0;
+  const int R = rle_rows(H);
+  const int64_t U = (int64_t)W * ((H + R - 1) / R);
+  return 4 * U < (1ll << 31) ? (int)U : 0;
+}
+
+static int rle_check(int N, int H, int W, const char* who) {
+  VG_CHECK(N > 0 && N <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && vg_mask_rle_units(H, W) > 0, VG_ERR_ARG,
+           "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+  return VG_OK;
+}
+
+static inline int rle_groups(int W) { return ((W + RLE_G - 1) / RLE_G + 63) / 64; }      // workgroups of 64 lanes per mask
+
+extern "C" int vg_mask_rle_count(const uint8_t* mask, int32_t* ws_cols, int32_t* n_runs, int N, int H, int W, vg_stream_t stream) {
+  VG_CHECK(mask && ws_cols && n_runs, VG_ERR_ARG, "vg_mask_rle_count: null pointer");
+  if (int e = rle_check(N, H, W, "vg_mask_rle_count")) return e;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = rle_rows(H), S = (H + R - 1) / R;
+  rle_count_kernel<<<dim3(rle_groups(W), S, N), 64, 0, st>>>(mask, ws_cols, H, W, R);
+  rle_scan_kernel<<<N, 1024, 0, st>>>(ws_cols, n_runs, H, W, S, R);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_mask_rle_emit(const uint8_t* mask, const int32_t* ws_cols, const int64_t* offsets, int32_t* counts, int N, int H, int W,
+                                vg_stream_t stream) {
+  VG_CHECK(mask && ws_cols && offsets && counts, VG_ERR_ARG, "vg_mask_rle_emit: null pointer");
+  if (int e = rle_check(N, H, W, "vg_mask_rle_emit")) return e;
+  const int R = rle_rows(H), S = (H + R - 1) / R;
+  rle_emit_kernel<<<dim3(rle_groups(W), S, N), 64, 0, (hipStream_t)stream>>>(mask, ws_cols, offsets, counts, H, W, R);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_rle_to_mask(const int32_t* counts, const int64_t* offsets, uint8_t* out, int32_t* status, int32_t* ws_ends, int N, int H,
+                              int W, vg_stream_t stream) {
+  // counts / ws_ends may be null when every code is empty (offsets all equal): such codes are refused and nothing is read
+  VG_CHECK(offsets && out && status && (!counts == !ws_ends), VG_ERR_ARG, "vg_rle_to_mask: null pointer");
+  if (int e = rle_check(N, H, W, "vg_rle_to_mask")) return e;
+  hipStream_t st = (hipStream_t)stream;
+  rle_ends_kernel<<<N, 256, 0, st>>>(counts, offsets, ws_ends, status, H * W);
+  const int rows = rle_rows(H);
+  rle_gather_kernel<<<dim3(rle_groups(W), (H + rows - 1) / rows, N), 64, 0, st>>>(ws_ends, offsets, status, out, H, W, rows);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }

@@ -148,6 +148,9 @@ class VideoGLaMMForCausalLM:
         # of a _binarize that filtered the blobs and reduced the boxes in one chain
         self._want_boxes = False
         self._fused = None
+        # this call's return_rle / return_masks (same life cycle): run-length codes as one more return value, and whether the dense masks are downloaded
+        self._want_rle = False
+        self._want_masks = True
         # diagnostics only: when set to a dict, inference() leaves the fp32 mask logits ("logits", device), the [SEG] embeddings
         # ("emb") and the model's own per-step argmaxes ("argmax") in it (bench.py's self-check, tests)
         self.capture = None
@@ -290,26 +293,42 @@ class VideoGLaMMForCausalLM:
 
     # ------------------------------------------------------------------ inference surface
     def inference(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                  max_new_tokens=32, use_sam2_video_branch=False, *, return_boxes=False, **sampling):
+                  max_new_tokens=32, use_sam2_video_branch=False, *, return_boxes=False, return_rle=False, return_masks=True, **sampling):
         """R/model/VideoGLaMM.py:560-596.  Keyword-only extras: do_sample / temperature / top_k / top_p (override model.generation_config for
         this call), generator (the torch.Generator the sampling seed is drawn from) and return_boxes: a third return value
         [{frame: {obj: np.float32[4]}}] with the keys of the masks' dictionaries, the postproc.masks_to_boxes value (x_min, y_min, x_max, y_max;
-        [1e8, 1e8, 0, 0] for an empty mask) of exactly the mask that is returned, reduced on the device before the masks are downloaded."""
+        [1e8, 1e8, 0, 0] for an empty mask) of exactly the mask that is returned, reduced on the device before the masks are downloaded.
+        return_rle: one more return value after that, [{frame: {obj: {"size": [H, W], "counts": [int, ...]}}}], COCO's uncompressed run-length code
+        (postproc.mask_to_rle_pytorch's form) of the same masks, encoded on the device by one ops.mask_rle call for the whole clip.
+        return_masks=False (needs return_boxes or return_rle): the dense masks are not downloaded; the mask dictionaries keep their keys and hold None."""
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             torch.cuda.set_device(self.device)
         if use_sam2_video_branch:
             if self.config.use_sam2:
                 return self.inference_video_branch(images, context_images, images_for_sam, input_ids, resize_list,
-                                                   original_size_list, max_new_tokens, return_boxes=return_boxes, **sampling)
+                                                   original_size_list, max_new_tokens, return_boxes=return_boxes, return_rle=return_rle,
+                                                   return_masks=return_masks, **sampling)
             raise ValueError("use_sam2_video_branch is True, but model is not configured to use SAM2")
         return self.inference_framewise(images, context_images, images_for_sam, input_ids, resize_list,
-                                        original_size_list, max_new_tokens, return_boxes=return_boxes, **sampling)
+                                        original_size_list, max_new_tokens, return_boxes=return_boxes, return_rle=return_rle,
+                                        return_masks=return_masks, **sampling)
 
-    def _set_return_boxes(self, return_boxes):
+    def _set_returns(self, return_boxes, return_rle=False, return_masks=True):
+        """this call's return_boxes / return_rle / return_masks; refusals come first, before any GPU work"""
+        if not return_masks and not (return_boxes or return_rle):
+            raise ValueError("return_masks=False needs return_boxes=True or return_rle=True: the call would return nothing about the masks")
         if return_boxes and self.comm is not None:
             raise NotImplementedError("return_boxes runs on one GPU: the masks of a multi-GPU model are sharded over the ranks; "
                                       "use postproc.masks_to_boxes on the returned masks")
+        if (return_rle or not return_masks) and self.comm is not None:
+            raise NotImplementedError("return_rle / return_masks=False run on one GPU: the masks of a multi-GPU model are sharded over the ranks; "
+                                      "use postproc.mask_to_rle_pytorch on the returned masks")
         self._want_boxes, self._fused = bool(return_boxes), None
+        self._want_rle, self._want_masks = bool(return_rle), bool(return_masks)
+
+    def _returns(self):
+        """the three keywords of this call, to hand on to a nested call"""
+        return dict(return_boxes=self._want_boxes, return_rle=self._want_rle, return_masks=self._want_masks)
 
     def _resolve_sampling(self, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
         """this call's decoding mode; multi-GPU: every rank adopts rank 0's seed (the decode is replicated and must emit the same ids)"""
@@ -393,24 +412,55 @@ class VideoGLaMMForCausalLM:
         return out
 
     def _download(self, masks):
-        """device uint8 masks [T,N,H,W] -> (host masks, None) or, under return_boxes, (host masks, float32 ndarray [T,N,4]): the boxes of all
-        T x N masks from ONE ops.mask_boxes call on the device masks, enqueued before the download (16 bytes per mask cross PCIe on top of the masks)."""
-        if not self._want_boxes:
-            return self._to_host(masks), None
-        from .postproc import boxes_xyxy
+        """device uint8 masks [T,N,H,W] -> (host masks, boxes, codes).  boxes: None or, under return_boxes, float32 ndarray [T,N,4], the boxes of
+        all T x N masks from ONE ops.mask_boxes call on the device masks, enqueued before the download (16 bytes per mask cross PCIe on top of the
+        masks).  codes: None or, under return_rle, the [T][N] run-length codes of the same masks from ONE ops.mask_rle call (its counts and offsets
+        are the two downloads).  Under return_masks=False the dense download is skipped and (T, N) stands in for the host masks."""
+        if not (self._want_boxes or self._want_rle):
+            return self._to_host(masks), None, None
+        boxes = codes = None
         fused, self._fused = self._fused, None
-        table = fused[1] if fused is not None and fused[0] is masks else ops.mask_boxes(masks)
-        boxes = boxes_xyxy(table)
-        return self._to_host(masks), boxes.cpu().numpy()
+        if self._want_boxes:
+            from .postproc import boxes_xyxy
+            table = fused[1] if fused is not None and fused[0] is masks else ops.mask_boxes(masks)
+            boxes = boxes_xyxy(table)
+        if self._want_rle:
+            counts, offsets = ops.mask_rle(masks)
+        host = self._to_host(masks) if self._want_masks else tuple(masks.shape[:2])
+        if self._want_boxes:
+            boxes = boxes.cpu().numpy()
+        if self._want_rle:
+            from .postproc import _split_rle
+            T, N = masks.shape[:2]
+            flat = _split_rle(counts.cpu(), offsets.cpu(), masks.shape[-2:])
+            codes = [flat[i * N:(i + 1) * N] for i in range(T)]
+        return host, boxes, codes
 
-    def _result(self, host, boxes):
-        """the tail of an inference()'s return value: ([segments],) or, under return_boxes, ([segments], [boxes]) with the same keys"""
-        if host is None:            # no [SEG]
-            return ([{}], [{}]) if self._want_boxes else ([{}],)
-        segs = self._segments(host)
-        if not self._want_boxes:
-            return ([segs],)
-        return [segs], [{t: {k: boxes[i, j] for j, k in enumerate(fr)} for i, (t, fr) in enumerate(segs.items())}]
+    def _extras(self):
+        """how many return values follow the masks: the boxes, then the codes"""
+        return int(self._want_boxes) + int(self._want_rle)
+
+    @staticmethod
+    def _cut(host, boxes, codes, a, n):
+        """objects [a, a + n) of a _download triple"""
+        return (host[:, a:a + n] if torch.is_tensor(host) else (host[0], n), None if boxes is None else boxes[:, a:a + n],
+                None if codes is None else [row[a:a + n] for row in codes])
+
+    def _result(self, host, boxes=None, codes=None):
+        """the tail of an inference()'s return value: ([segments],) and, with the same keys, [boxes] under return_boxes and [codes] under
+        return_rle, in that order.  host: _download's first value; None = no [SEG]."""
+        if host is None:
+            return tuple([{}] for _ in range(1 + self._extras()))
+        if torch.is_tensor(host):
+            segs = self._segments(host)
+        else:                       # return_masks=False: the keys, no pixels
+            segs = {t: {k: None for k in range(host[1])} for t in range(host[0])}
+        out = [[segs]]
+        if self._want_boxes:
+            out.append([{t: {k: boxes[i, j] for j, k in enumerate(fr)} for i, (t, fr) in enumerate(segs.items())}])
+        if self._want_rle:
+            out.append([{t: {k: codes[i][j] for j, k in enumerate(fr)} for i, (t, fr) in enumerate(segs.items())}])
+        return tuple(out)
 
     def _hiera_async(self, sam, frames=None, all_frames=False, bufs=None):
         """Hiera + FPN of the SAM frames on a side HIP stream.  It depends only on the pixels, not on the LLM, and it is
@@ -437,15 +487,15 @@ class VideoGLaMMForCausalLM:
 
     def inference_framewise(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
                             max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None, empty_ok=False,
-                            return_boxes=False):
+                            return_boxes=False, return_rle=False, return_masks=True):
         """R/model/VideoGLaMM.py:598-768 -> (output_ids [1,L+G], [ {frame: {obj: mask}} ]).  empty_ok: no [SEG] gives [{}] as the video branch
-        does, not the reference's exception (inference_prompts' meaning of such a prompt).  return_boxes: see inference()."""
-        self._set_return_boxes(return_boxes)
+        does, not the reference's exception (inference_prompts' meaning of such a prompt).  return_boxes / return_rle / return_masks: see inference()."""
+        self._set_returns(return_boxes, return_rle, return_masks)
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens)
         if emb.shape[0] == 0 and empty_ok:
-            return (out_ids,) + self._result(None, None)
+            return (out_ids,) + self._result(None)
         if emb.shape[0] == 0:
             # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
             raise AttributeError("'tuple' object has no attribute 'shape'")
@@ -457,20 +507,20 @@ class VideoGLaMMForCausalLM:
             stage_mark(self.stages, "mask_decode")
             return out_ids, [self._segments(host, frame_ids=fids)]
         elif self._fast_masks():
-            masks, boxes = self._download(self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=True)[0])
+            res = self._download(self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats, as_masks=True)[0])
             stage_mark(self.stages, "mask_decode")
         else:
             logits, _ = self.sam2.framewise_branch(sam, emb, hw, frame_feats=feats)
             if self.capture is not None:
                 self.capture["logits"] = logits
-            masks, boxes = self._download(self._binarize(logits))
-        return (out_ids,) + self._result(masks, boxes)
+            res = self._download(self._binarize(logits))
+        return (out_ids,) + self._result(*res)
 
     def inference_video_branch(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
                                max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None,
-                               return_boxes=False):
-        """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842).  return_boxes: see inference()."""
-        self._set_return_boxes(return_boxes)
+                               return_boxes=False, return_rle=False, return_masks=True):
+        """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842).  return_boxes / return_rle / return_masks: see inference()."""
+        self._set_returns(return_boxes, return_rle, return_masks)
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         # multi-GPU: frames shard for Hiera only (the propagation is a recurrence over frames) and every rank needs every frame's features:
@@ -480,7 +530,7 @@ class VideoGLaMMForCausalLM:
         graphed = self.comm is None and self.device.type == "cuda" and os.environ.get("VG_VIDEO_GRAPH", "1") == "1"
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens, all_frames=streamed, static_feats=graphed)
         if emb.shape[0] == 0:
-            return (out_ids,) + self._result(None, None)
+            return (out_ids,) + self._result(None)
         hw = tuple(original_size_list[0])
         if self.comm is not None:
             # OBJECTS shard for the propagation
@@ -498,14 +548,14 @@ class VideoGLaMMForCausalLM:
             fast = self._fast_masks()
             out = self.sam2.video_branch_graphed(sam, emb, hw, feats, as_masks=fast)
             if fast:
-                host, boxes = self._download(out)
+                res = self._download(out)
                 stage_mark(self.stages, "propagation")
-                return (out_ids,) + self._result(host, boxes)
+                return (out_ids,) + self._result(*res)
             logits = out
         elif self._fast_masks():
-            host, boxes = self._download(self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=True))
+            res = self._download(self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=True))
             stage_mark(self.stages, "propagation")
-            return (out_ids,) + self._result(host, boxes)
+            return (out_ids,) + self._result(*res)
         else:
             logits = self.sam2.video_branch(sam, emb, hw, frame_feats=feats)
         if self.capture is not None:
@@ -515,9 +565,10 @@ class VideoGLaMMForCausalLM:
     # ------------------------------------------------------------------ several prompts about one clip
     def inference_prompts(self, images, context_images, images_for_sam, input_ids_list, resize_list, original_size_list,
                           max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                          generator=None, shared=None, return_boxes=False):
+                          generator=None, shared=None, return_boxes=False, return_rle=False, return_masks=True):
         """B prompts ([1, L_b] or [L_b] each) about ONE clip -> (output ids [1, L_b + G_b] per prompt, {frame: {obj: mask}} per prompt).
-        return_boxes adds a third list, {frame: {obj: np.float32[4]}} per prompt (see inference(); {} where the masks are {}).
+        return_boxes adds a third list, {frame: {obj: np.float32[4]}} per prompt (see inference(); {} where the masks are {}); return_rle one more
+        after it, {frame: {obj: code}} per prompt; return_masks=False leaves None in the mask dictionaries (see inference()).
         Entry b means what inference(..., input_ids=input_ids_list[b]) means; a prompt without a [SEG] gets {} (as the video branch does,
         R/model/VideoGLaMM.py:840-842).  The towers, Hiera and the prefill of the shared prefix (system text + visual block, identical ids in
         every prompt) run once; SAM2 runs once with every prompt's [SEG] embeddings as its objects.  Sampling draws one seed per prompt from
@@ -529,7 +580,7 @@ class VideoGLaMMForCausalLM:
         from .prompts import GROUP, check_prompts
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_prompts() runs on one GPU: call inference() per prompt on a multi-GPU model")
-        self._set_return_boxes(return_boxes)
+        self._set_returns(return_boxes, return_rle, return_masks)
         ids_list = [torch.as_tensor(x).cpu().long() for x in input_ids_list]
         if not ids_list:
             raise NotImplementedError("inference_prompts() needs at least one prompt")
@@ -549,21 +600,22 @@ class VideoGLaMMForCausalLM:
         if not shared:
             return self._prompts_alone(images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens,
                                        use_sam2_video_branch, dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                                                   generator=generator, return_boxes=self._want_boxes))
+                                                                   generator=generator, **self._returns()))
         samplings = [resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator) for _ in ids_list]
-        out_ids, segs, boxes = [], [], []
+        out_ids, segs, extras = [], [], [[] for _ in range(self._extras())]
         for g in range(0, len(ids_list), GROUP):
-            o, s, b = self._prompts_group(images, context_images, images_for_sam, ids_list[g:g + GROUP], original_size_list, max_new_tokens,
-                                          use_sam2_video_branch, samplings[g:g + GROUP])
+            o, s, ex = self._prompts_group(images, context_images, images_for_sam, ids_list[g:g + GROUP], original_size_list, max_new_tokens,
+                                           use_sam2_video_branch, samplings[g:g + GROUP])
             out_ids += o
             segs += s
-            boxes += b
-        return (out_ids, segs, boxes) if self._want_boxes else (out_ids, segs)
+            for acc, e in zip(extras, ex):
+                acc += e
+        return (out_ids, segs, *extras)
 
     def _prompts_alone(self, images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens, video, sampling):
         """inference_prompts() as one inference() per prompt, in list order (each call draws its own sampling seed from the generator); the
         captures of the calls are gathered per prompt as _prompts_group leaves them."""
-        out_ids, segs, boxes, caps = [], [], [], []
+        out_ids, segs, extras, caps = [], [], [[] for _ in range(self._extras())], []
         keep = self.capture
         try:
             for ids in ids_list:
@@ -577,7 +629,8 @@ class VideoGLaMMForCausalLM:
                                                         max_new_tokens, empty_ok=True, **sampling)
                 out_ids.append(o)
                 segs.append(s[0])
-                boxes += [x[0] for x in b]
+                for acc, x in zip(extras, b):
+                    acc.append(x[0])
                 caps.append(self.capture)
         finally:
             self.capture = keep
@@ -585,7 +638,7 @@ class VideoGLaMMForCausalLM:
             for k in ("argmax", "emb", "logits"):
                 if any(k in c for c in caps):
                     keep[k] = [c.get(k) for c in caps]
-        return (out_ids, segs, boxes) if sampling["return_boxes"] else (out_ids, segs)
+        return (out_ids, segs, *extras)
 
     def _prompts_group(self, images, context_images, images_for_sam, ids_list, original_size_list, max_new_tokens, video, samplings):
         from .prompts import generate_prompts
@@ -622,7 +675,7 @@ class VideoGLaMMForCausalLM:
             self.capture["argmax"] = [t.get("argmax", []) for t in traces]
             self.capture["emb"] = [emb[a:a + n] for a, n in zip(starts, counts)]
         if emb.shape[0] == 0:
-            return out, [{} for _ in ids_list], [{} for _ in ids_list]
+            return out, [{} for _ in ids_list], [[{} for _ in ids_list] for _ in range(self._extras())]
         hw = tuple(original_size_list[0])
         fast = self._fast_masks()
         if video:
@@ -636,18 +689,18 @@ class VideoGLaMMForCausalLM:
             if self.capture is not None:
                 self.capture["logits"] = [res[:, a:a + n] for a, n in zip(starts, counts)]
             res = self._binarize(res)
-        host, boxes = self._download(res)
+        down = self._download(res)
         stage_mark(self.stages, "propagation" if video else "mask_decode")
-        # objects [a, a + n) are prompt b's, renumbered from 0 (the third list stays empty without return_boxes)
-        per = [self._result(host[:, a:a + n], None if boxes is None else boxes[:, a:a + n]) if n else self._result(None, None)
-               for a, n in zip(starts, counts)]
-        return out, [p[0][0] for p in per], [p[1][0] for p in per if self._want_boxes]
+        # objects [a, a + n) are prompt b's, renumbered from 0; one list per extra return value (boxes, codes) follows the masks
+        per = [self._result(*self._cut(*down, a, n)) if n else self._result(None) for a, n in zip(starts, counts)]
+        return out, [p[0][0] for p in per], [[p[i][0] for p in per] for i in range(1, 1 + self._extras())]
 
     # ------------------------------------------------------------------ several clips, one prompt each
     def inference_clips(self, clips, max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                        generator=None, return_boxes=False):
+                        generator=None, return_boxes=False, return_rle=False, return_masks=True):
         """B clips, one prompt each -> a list whose entry b is what inference(*clips[b], max_new_tokens, use_sam2_video_branch, ...) returns
-        (with return_boxes: inference()'s third element, [{frame: {obj: np.float32[4]}}], in every clip's tuple):
+        (with return_boxes: inference()'s third element, [{frame: {obj: np.float32[4]}}], in every clip's tuple; with return_rle its codes after
+        that; return_masks=False as in inference()):
         (output ids [1, L_b + G_b], [{frame: {obj: mask}}]), the same ids and the same masks pixel for pixel.  clips[b]: the six per-clip arguments
         of inference() (images, context_images, images_for_sam, input_ids, resize_list, original_size_list) as a tuple or a dict.
         Every clip runs its own towers, Hiera and whole-prompt prefill; the clips of a group (up to 16) then decode together, one row per clip in
@@ -658,7 +711,7 @@ class VideoGLaMMForCausalLM:
         from .clips import as_clip, groups
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_clips() runs on one GPU: call inference() per clip on a multi-GPU model")
-        self._set_return_boxes(return_boxes)
+        self._set_returns(return_boxes, return_rle, return_masks)
         clips = [as_clip(c, b) for b, c in enumerate(clips)]
         if not clips:
             raise NotImplementedError("inference_clips() needs at least one clip")
@@ -712,7 +765,7 @@ class VideoGLaMMForCausalLM:
         """the single-GPU mask decode of inference_video_branch / inference_framewise for one clip (capture unset): _result's tuple"""
         if emb.shape[0] == 0:
             if video:
-                return self._result(None, None)
+                return self._result(None)
             # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
             raise AttributeError("'tuple' object has no attribute 'shape'")
         fast = self._fast_masks()

@@ -1752,6 +1752,48 @@ def mask_boxes(masks, min_size=0, return_mask=False):
     return (out, kept) if return_mask else out
 
 
+def mask_rle(masks):
+    """masks [..., H, W] bool/uint8 -> (counts int32 [total], offsets int64 [prod(lead) + 1]): COCO's uncompressed run-length
+    code of every mask in mask_to_rle_pytorch's form (column-major pixel order, a leading 0 when pixel 0 is foreground); mask n's
+    counts are counts[offsets[n] : offsets[n + 1]].  Count, a cumsum, ONE 8-byte read of the total (it sizes the output), emit."""
+    lib = _lib.load()
+    m = _u8(masks)
+    H, W = m.shape[-2:]
+    N = m.numel() // (H * W) if H * W else 0
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=m.device)
+    if N == 0:
+        return torch.empty(0, dtype=torch.int32, device=m.device), offsets
+    ws = torch.empty((N, 4, max(lib.vg_mask_rle_units(H, W), 1)), dtype=torch.int32, device=m.device)
+    n_runs = torch.empty(N, dtype=torch.int32, device=m.device)
+    _lib.check(lib.vg_mask_rle_count(_p(m), _p(ws), _p(n_runs), N, H, W, _stream()), "vg_mask_rle_count")
+    torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[-1])
+    if total >= 2 ** 31:
+        raise ValueError(f"mask_rle: {total} runs in one call do not fit int32 indexing; encode fewer masks per call")
+    counts = torch.empty(total, dtype=torch.int32, device=m.device)
+    _lib.check(lib.vg_mask_rle_emit(_p(m), _p(ws), _p(offsets), _p(counts), N, H, W, _stream()), "vg_mask_rle_emit")
+    return counts, offsets
+
+
+def rle_to_mask(counts, offsets, H, W):
+    """counts int32 [total], offsets int64 [n + 1] -> (uint8 [n, H, W] of 0 / 1, status int32 [n]).  status[i] = 1 and mask i all zero when
+    a count of code i is negative or its counts do not sum to H * W.  The offsets are checked here (one small read): the kernel reads
+    counts through them."""
+    lib = _lib.load()
+    counts, offsets = counts.contiguous(), offsets.contiguous()
+    assert counts.dtype == torch.int32 and offsets.dtype == torch.int64 and counts.dim() == 1 and offsets.dim() == 1 and offsets.numel() >= 1
+    n = offsets.numel() - 1
+    if not bool((offsets[0] == 0) & (offsets[1:] >= offsets[:-1]).all() & (offsets[-1] == counts.numel())):
+        raise ValueError("rle_to_mask: offsets must start at 0, not decrease, and end at len(counts)")
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=counts.device)
+    status = torch.empty(n, dtype=torch.int32, device=counts.device)
+    if n == 0:
+        return out, status
+    ends = torch.empty_like(counts)
+    _lib.check(lib.vg_rle_to_mask(_p(counts), _p(offsets), _p(out), _p(status), _p(ends), n, H, W, _stream()), "vg_rle_to_mask")
+    return out, status
+
+
 # ---------------------------------------------------------------- image pre-processing on the device (§8f-1)
 def resample_u8(x, out_size, axis, bounds, coeffs):
     """one pass of Pillow's 8-bit resampler over x [N,H,W,C] uint8; bounds [out,2] / coeffs [out,ksize] int32 on device."""

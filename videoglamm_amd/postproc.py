@@ -15,6 +15,9 @@ pairing of compute_miou, the F formula) is the reference's float64 host arithmet
   np_box_area / np_box_iou     R/utils/grounding_utils/box_ops.py:12-62     (the reference's numpy arithmetic, on the host)
   calc_tiou                    R/eval_grounding.py:55-72                    (_calc_tiou)
   video_grounding_metrics      R/eval_grounding.py:326-405                  (the per-video record of the VidSTG / HC-STVG driver)
+  mask_to_rle_pytorch / rle_to_mask / area_from_rle / coco_encode_rle
+                               R/model/segment_anything_2/sam2/utils/amg.py:109-155, 296-302   (coco_decode_rle, the compressed string
+                               as input and device= are this build's extensions; the string codec is pycocotools' rule, in Python)
 """
 import numpy as np
 import torch
@@ -221,3 +224,103 @@ def video_grounding_metrics(pred_boxes, gt_boxes, gt_sted, frame_ids, pred_sted=
     rec["gt_viou"] = gt_viou
     rec.update({f"gt_viou@{t}": int(gt_viou > t) for t in iou_thresholds})
     return rec
+
+
+# ---------------------------------------------------------------- run-length codes (COCO RLE): the form masks are stored and exchanged in
+def _split_rle(counts, offsets, size):
+    """host counts / offsets of ops.mask_rle -> one {"size", "counts"} per mask"""
+    c, o = counts.tolist(), offsets.tolist()
+    return [{"size": list(size), "counts": c[a:b]} for a, b in zip(o[:-1], o[1:])]
+
+
+def mask_to_rle_pytorch(masks):
+    """[N, H, W] masks -> [{"size": [h, w], "counts": [int, ...]}, ...], COCO's uncompressed RLE: runs of the column-major pixel order,
+    background first (a leading 0 when pixel 0 is foreground).  Encoded where the masks are (ops.mask_rle); the counts cross PCIe."""
+    m = _mask(masks)
+    assert m.dim() == 3, "mask_to_rle_pytorch takes [N, H, W]"
+    if m.shape[0] == 0:
+        return []
+    counts, offsets = ops.mask_rle(m)
+    return _split_rle(counts.cpu(), offsets.cpu(), m.shape[-2:])
+
+
+def coco_encode_rle(rle):
+    """uncompressed code -> {"size", "counts": str}: pycocotools' rleToString.  Each count (minus the count two places back from the fourth
+    on) goes out in 5-bit groups, low group first; bit 5 of a character says that another group follows, and bit 4 of the last group is
+    the sign.  Pinned to this statement and to the vector in the tests: pycocotools itself is not a dependency."""
+    cnts = rle["counts"]
+    if isinstance(cnts, (str, bytes)):
+        return {"size": list(rle["size"]), "counts": cnts if isinstance(cnts, str) else cnts.decode("ascii")}
+    s = []
+    for i, x in enumerate(cnts):
+        x = int(x)
+        if i > 2:
+            x -= int(cnts[i - 2])
+        more = True
+        while more:
+            c = x & 0x1f
+            x >>= 5
+            more = (x != -1) if c & 0x10 else (x != 0)
+            if more:
+                c |= 0x20
+            s.append(chr(c + 48))
+    return {"size": list(rle["size"]), "counts": "".join(s)}
+
+
+def coco_decode_rle(rle):
+    """{"size", "counts": str or bytes} -> uncompressed code: pycocotools' rleFrString.  A code that already holds a count list is copied."""
+    s = rle["counts"]
+    if not isinstance(s, (str, bytes)):
+        return {"size": list(rle["size"]), "counts": [int(v) for v in s]}
+    if isinstance(s, str):
+        s = s.encode("ascii")
+    cnts, p = [], 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            if p >= len(s):
+                raise ValueError("coco_decode_rle: the string ends inside a count")
+            c = s[p] - 48
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and c & 0x10:
+                x |= -1 << (5 * k)
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x)
+    return {"size": list(rle["size"]), "counts": cnts}
+
+
+def area_from_rle(rle):
+    return sum(coco_decode_rle(rle)["counts"][1::2])
+
+
+def rle_to_mask(rle, device=None):
+    """One code -> bool ndarray [h, w] (the reference's value); a list of codes -> a list of them.  Codes hold count lists or compressed
+    strings.  device: keep the result there and return bool device tensor(s), so that a stored ground truth reaches the metrics of this
+    module as its counts (kilobytes) and not as a dense upload.  Decoded on the device (ops.rle_to_mask), all codes of one size in one call;
+    a code with a negative count, or whose counts do not sum to h * w, raises ValueError."""
+    single = isinstance(rle, dict)
+    codes = [coco_decode_rle(r) for r in ([rle] if single else rle)]
+    dev = torch.device(DEVICE if device is None else device)
+    out = [None] * len(codes)
+    by_size = {}
+    for i, r in enumerate(codes):
+        by_size.setdefault(tuple(int(v) for v in r["size"]), []).append(i)
+    for (h, w), ids in by_size.items():
+        lens = [len(codes[i]["counts"]) for i in ids]
+        flat = [v for i in ids for v in codes[i]["counts"]]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in flat):
+            raise ValueError("rle_to_mask: a count does not fit int32")
+        counts = torch.tensor(flat, dtype=torch.int32).to(dev)
+        offsets = torch.tensor(np.concatenate(([0], np.cumsum(lens, dtype=np.int64))), dtype=torch.int64).to(dev)
+        masks, status = ops.rle_to_mask(counts, offsets, h, w)
+        bad = status.cpu().nonzero().flatten().tolist()
+        if bad:
+            raise ValueError(f"rle_to_mask: the counts of code {ids[bad[0]]} are negative or do not sum to {h} * {w}")
+        masks = masks.view(torch.bool) if device is not None else masks.cpu().numpy().view(bool)
+        for k, i in enumerate(ids):
+            out[i] = masks[k]
+    return out[0] if single else out

@@ -178,3 +178,14 @@ extern "C" void vg_set_error(const char* fmt, ...);
       return VG_ERR_LAUNCH;                                            \
     }                                                                  \
   } while (0)
+
+// Dynamic LDS past 64 KB has to be allowed per kernel: raise KERNEL's cap when a launch needs more than any launch before it (never inside a
+// graph replay: the capture has made the call).  One cap per kernel instantiation.
+template <auto KERNEL>
+inline void vg_raise_lds_cap(size_t lds) {
+  static size_t cap = 64 * 1024;
+  if (lds > cap) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    cap = lds;
+  }
+}

@@ -6,6 +6,7 @@
 //                         workgroup to finish (no separate rope / combine launches)
 // Arithmetic mirrors the stand-alone kernels (vg_rmsnorm, vg_gemm skinny path, vg_rope_kv_append) step for step.
 #include "vg_common.h"
+#include "vg_decode_launch.h"
 #include <type_traits>
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -478,20 +479,7 @@ __global__ __launch_bounds__(256) void decode_gemv_kernel(DecGemvArgs p) {
 template <typename T, typename TO, bool GLU>
 static int launch_decode_gemv(DecGemvArgs p, hipStream_t st) {
   constexpr int KPC = 16 / sizeof(T);
-  static int bpc = -1;
-  if (bpc < 0) {
-    // max workgroups per CU the row pairs are spread over (measured constant).  2 = what is resident (these kernels take 254 VGPRs): with 4 the q|k|v
-    // projection ran 768 workgroups in one and a half rounds (r03: 3.23 -> 3.205 ms per token on C2)
-    bpc = 2;
-  }
-  const int npair = GLU ? p.N : (p.N + 1) / 2;
-  const int maxw = 256 * bpc * 4;
-  int ppw = (npair + maxw - 1) / maxw;              // row pairs per wave
-  // prefer a split that gives every CU the same number of workgroups (a multiple of 256 workgroups)
-  for (int c = ppw; c <= 2 * ppw; ++c)
-    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
-  if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
-  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
+  const auto [ppw, blocks] = dec_pair_split(GLU ? p.N : (p.N + 1) / 2, 2, DEC_MAX_PPW);
   p.ppw = ppw;
   const size_t lds = (size_t)p.K * sizeof(T);
   const int nch = p.K / KPC;
@@ -515,17 +503,7 @@ static int launch_decode_gemv(DecGemvArgs p, hipStream_t st) {
 
 template <typename TO, bool GLU>
 static int launch_decode_gemv_w8(DecGemvArgs p, hipStream_t st) {
-  static int bpc = -1;
-  if (bpc < 0) {
-    bpc = 4;
-  }
-  const int npair = GLU ? p.N : (p.N + 1) / 2;
-  const int maxw = 256 * bpc * 4;
-  int ppw = (npair + maxw - 1) / maxw;
-  for (int c = ppw; c <= 2 * ppw; ++c)
-    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
-  if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
-  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
+  const auto [ppw, blocks] = dec_pair_split(GLU ? p.N : (p.N + 1) / 2, 4, DEC_MAX_PPW);
   p.ppw = ppw;
   const size_t lds = (size_t)p.K * 2;
   const int nchw = p.K / 16;               // weight chunks per row
@@ -699,13 +677,7 @@ extern "C" int vg_decode_gemv_p13_supported(int K) { return K == 4096 || K == 14
 
 template <typename TO, bool GLU>
 static int launch_decode_gemv_p13(DecGemvArgs p, hipStream_t st) {
-  const int npair = GLU ? p.N : (p.N + 1) / 2;
-  const int maxw = 256 * 2 * 4;                              // launch_decode_gemv's split (two workgroups per CU)
-  int ppw = (npair + maxw - 1) / maxw;
-  for (int c = ppw; c <= 2 * ppw; ++c)
-    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
-  if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
-  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
+  const auto [ppw, blocks] = dec_pair_split(GLU ? p.N : (p.N + 1) / 2, 2, DEC_MAX_PPW);
   p.ppw = ppw;
   const size_t lds = (size_t)p.K * 2;
   if (p.K == 4096) decode_gemv_fast_kernel<bf16_t, TO, GLU, 2, 4, false, 0, true><<<blocks, 256, lds, st>>>(p);
@@ -744,47 +716,46 @@ extern "C" int vg_decode_qkv_rope_supported(int H, int Hkv, int D, int K, int dt
 
 template <typename T, int NB, typename KVO = T>
 static int launch_decode_qkv_rope(DecGemvArgs p, hipStream_t st) {
-  const int npair = p.N / 2;
-  const int maxw = 256 * 2 * 4;
-  int ppw = (npair + maxw - 1) / maxw;
-  for (int c = ppw; c <= 2 * ppw; ++c)
-    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
-  if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
+  const auto [ppw, blocks] = dec_pair_split(p.N / 2, 2, DEC_MAX_PPW);
   p.ppw = ppw;
-  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
   decode_gemv_fast_kernel<T, T, false, NB, 4, false, 64, false, KVO><<<blocks, 256, (size_t)p.K * sizeof(T), st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
 
+// fn: the entry point's name for the messages.  KV: the caches' element type — void = the activation dtype, kv8_t = e4m3 codes (kv_cache =
+// "fp8_rope", DESIGN 8c: bf16 activations only; the same kernel, the key / value pairs stored by kv8_store_pair, q_out with the bf16 cache's bits)
+template <typename KV>
+static int decode_qkv_rope(const char* fn, const void* x, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, void* k_cache,
+                           void* v_cache, const float* rope_cs, const int* pos_dev, int H, int Hkv, int D, int K, int dtype, vg_stream_t stream) {
+  constexpr bool KV8 = std::is_same<KV, kv8_t>::value;
+  VG_CHECK(x && Wqkv && q_out && k_cache && v_cache && rope_cs && pos_dev, VG_ERR_ARG, "%s: null pointer", fn);
+  VG_CHECK((!KV8 || dtype == VG_BF16) && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
+           "%s: H=%d Hkv=%d D=%d K=%d dtype=%d not covered%s", fn, H, Hkv, D, K, dtype, KV8 ? " (bf16 only)" : "");
+  const int kpc = dtype == VG_BF16 ? 8 : 4;
+  VG_CHECK(ldw % kpc == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)Wqkv & 15) == 0 && ((uintptr_t)norm_w & 15) == 0, VG_ERR_ARG,
+           "%s: alignment (16 bytes; ldw a multiple of %d)", fn, kpc);
+  DecGemvArgs p{x, Wqkv, q_out, norm_w, nullptr, (H + 2 * Hkv) * D, K, ldw, eps, 1, nullptr, rope_cs, pos_dev, k_cache, v_cache, H, Hkv};
+  hipStream_t st = (hipStream_t)stream;
+  if constexpr (KV8) {
+    return K == 4096 ? launch_decode_qkv_rope<bf16_t, 2, kv8_t>(p, st) : launch_decode_qkv_rope<bf16_t, 1, kv8_t>(p, st);
+  } else {
+    if (dtype == VG_BF16) return K == 4096 ? launch_decode_qkv_rope<bf16_t, 2>(p, st) : launch_decode_qkv_rope<bf16_t, 1>(p, st);
+    return launch_decode_qkv_rope<float, 4>(p, st);
+  }
+}
+
 extern "C" int vg_decode_qkv_rope(const void* x, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, void* k_cache,
                                   void* v_cache, const float* rope_cs, const int* pos_dev, int H, int Hkv, int D, int K, int dtype,
                                   vg_stream_t stream) {
-  VG_CHECK(x && Wqkv && q_out && k_cache && v_cache && rope_cs && pos_dev, VG_ERR_ARG, "vg_decode_qkv_rope: null pointer");
-  VG_CHECK(vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED, "vg_decode_qkv_rope: H=%d Hkv=%d D=%d K=%d dtype=%d not covered", H, Hkv, D, K,
-           dtype);
-  const int kpc = dtype == VG_BF16 ? 8 : 4;
-  VG_CHECK(ldw % kpc == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)Wqkv & 15) == 0 && ((uintptr_t)norm_w & 15) == 0, VG_ERR_ARG,
-           "vg_decode_qkv_rope: alignment (16 bytes; ldw a multiple of %d)", kpc);
-  DecGemvArgs p{x, Wqkv, q_out, norm_w, nullptr, (H + 2 * Hkv) * D, K, ldw, eps, 1, nullptr, rope_cs, pos_dev, k_cache, v_cache, H, Hkv};
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VG_BF16) return K == 4096 ? launch_decode_qkv_rope<bf16_t, 2>(p, st) : launch_decode_qkv_rope<bf16_t, 1>(p, st);
-  return launch_decode_qkv_rope<float, 4>(p, st);
+  return decode_qkv_rope<void>("vg_decode_qkv_rope", x, Wqkv, ldw, norm_w, eps, q_out, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, K, dtype, stream);
 }
 
-// vg_decode_qkv_rope with e4m3 K/V destinations (kv_cache = "fp8_rope"): the same kernel, the key / value pairs stored by
-// kv8_store_pair; q_out has the bf16 entry point's bits
 extern "C" int vg_decode_qkv_rope_kv8(const void* x, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out, uint8_t* k_cache,
                                       uint8_t* v_cache, const float* rope_cs, const int* pos_dev, int H, int Hkv, int D, int K, int dtype,
                                       vg_stream_t stream) {
-  VG_CHECK(x && Wqkv && q_out && k_cache && v_cache && rope_cs && pos_dev, VG_ERR_ARG, "vg_decode_qkv_rope_kv8: null pointer");
-  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
-           "vg_decode_qkv_rope_kv8: H=%d Hkv=%d D=%d K=%d dtype=%d not covered (bf16 only)", H, Hkv, D, K, dtype);
-  VG_CHECK(ldw % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)Wqkv & 15) == 0 && ((uintptr_t)norm_w & 15) == 0, VG_ERR_ARG,
-           "vg_decode_qkv_rope_kv8: alignment (16 bytes; ldw a multiple of 8)");
-  DecGemvArgs p{x, Wqkv, q_out, norm_w, nullptr, (H + 2 * Hkv) * D, K, ldw, eps, 1, nullptr, rope_cs, pos_dev, k_cache, v_cache, H, Hkv};
-  hipStream_t st = (hipStream_t)stream;
-  return K == 4096 ? launch_decode_qkv_rope<bf16_t, 2, kv8_t>(p, st) : launch_decode_qkv_rope<bf16_t, 1, kv8_t>(p, st);
+  return decode_qkv_rope<kv8_t>("vg_decode_qkv_rope_kv8", x, Wqkv, ldw, norm_w, eps, q_out, k_cache, v_cache, rope_cs, pos_dev, H, Hkv, D, K, dtype,
+                                stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -987,28 +958,19 @@ static int launch_rows_b(DecRowsArgs p, hipStream_t st) {
   // x staging: the whole row when it fits the budget (always with the norm), else phases of batches with one pair per wave
   int nph = NB;
   if (!p.nw && (int64_t)BR * NB * BBYTES > DEC_ROWS_LDS) nph = max(1, DEC_ROWS_LDS / (BR * BBYTES));
-  int ppw = (npair + 2047) / 2048;                  // ~2 workgroups per CU, as vg_decode_gemv
-  ppw = nph < NB ? 1 : min(ppw, DEC_ROWS_PPW);
+  const auto [ppw, blocks] = dec_rows_split(npair, nph < NB, DEC_ROWS_PPW);
   p.nph = nph;
   p.ppw = ppw;
   const size_t lds = (size_t)BR * nph * BBYTES;
-  static size_t cap = 64 * 1024;
-  if (lds > 64 * 1024 && lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD, KVO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cap = lds;
-  }
-  decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD, KVO><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
+  vg_raise_lds_cap<decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD, KVO>>(lds);
+  decode_gemv_rows_kernel<TO, GLU, NB, BR, RHD, KVO><<<blocks, 256, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
 
 template <typename TO, bool GLU, int NB, int RHD, typename KVO = TO>
 static int launch_rows_nb(DecRowsArgs p, hipStream_t st) {
-  if (p.B <= 1) return launch_rows_b<TO, GLU, NB, 1, RHD, KVO>(p, st);
-  if (p.B <= 2) return launch_rows_b<TO, GLU, NB, 2, RHD, KVO>(p, st);
-  if (p.B <= 4) return launch_rows_b<TO, GLU, NB, 4, RHD, KVO>(p, st);
-  if (p.B <= 8) return launch_rows_b<TO, GLU, NB, 8, RHD, KVO>(p, st);
-  return launch_rows_b<TO, GLU, NB, 16, RHD, KVO>(p, st);
+  return dec_with_bucket(p.B, [&](auto br) { return launch_rows_b<TO, GLU, NB, decltype(br)::value, RHD, KVO>(p, st); });
 }
 
 template <bool GLU>
@@ -1025,11 +987,11 @@ static int launch_rows(DecRowsArgs p, hipStream_t st) {
 
 extern "C" int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
                                    const void* R, int64_t ldr, int N, int K, int B, int glu, int dtype, vg_stream_t stream) {
-  VG_CHECK(x && W && y && N > 0 && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemv_rows: bad args N=%d B=%d", N, B);
+  VG_CHECK(x && W && y && N > 0 && dec_rows_b_ok(B), VG_ERR_ARG, "vg_decode_gemv_rows: bad args N=%d B=%d", N, B);
   VG_CHECK(dtype == VG_BF16 && dec_rows_nb(K), VG_ERR_UNSUPPORTED, "vg_decode_gemv_rows: bf16 rows of K = 3072 or 2048 x {1, 2, 4, 7, 8} only (K=%d dtype=%d)", K, dtype);
   VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)W) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
            "vg_decode_gemv_rows: alignment (16 bytes; ldx / ldw multiples of 8)");
-  const int br = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;      // the bucket the kernel stages
+  const int br = dec_bucket(B);      // the bucket the kernel stages
   VG_CHECK(!norm_w || (int64_t)br * K * 2 <= 160 * 1024 - 8 * 1024, VG_ERR_UNSUPPORTED,
            "vg_decode_gemv_rows: the norm stages the whole rows of the %d-row bucket: B=%d K=%d do not fit", br, B, K);
   DecRowsArgs p{x, ldx, W, ldw, y, ldy, norm_w, eps, R, ldr, N, K, B, 1, 1};
@@ -1037,36 +999,40 @@ extern "C" int vg_decode_gemv_rows(const void* x, int64_t ldx, const void* W, in
   return glu ? launch_rows<true>(p, st) : launch_rows<false>(p, st);
 }
 
+// fn: the entry point's name for the messages.  KV: the slots' element type — bf16, or kv8_t = e4m3 codes: slot_stride in elements = bytes
+// (a multiple of 8, as the attention's loads need)
+template <typename KV>
+static int decode_qkv_rope_rows(const char* fn, const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out,
+                                int64_t ldq, void* k_slots, void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* rope_cs,
+                                const int* pos, int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream) {
+  VG_CHECK(x && Wqkv && q_out && k_slots && v_slots && rope_cs && pos && dec_rows_b_ok(B) && slot_rows > 0, VG_ERR_ARG,
+           "%s: bad args B=%d slot_rows=%d", fn, B, slot_rows);
+  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
+           "%s: H=%d Hkv=%d D=%d K=%d dtype=%d not covered", fn, H, Hkv, D, K, dtype);
+  const bool aligned = ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)Wqkv) | ((uintptr_t)norm_w)) & 15) == 0;
+  if constexpr (std::is_same<KV, kv8_t>::value)
+    VG_CHECK(aligned && slot_stride % 8 == 0 && slot_stride >= (int64_t)slot_rows * Hkv * D, VG_ERR_ARG,
+             "%s: alignment (16 bytes; ldx / ldw / slot_stride multiples of 8; slots must not overlap)", fn);
+  else
+    VG_CHECK(aligned, VG_ERR_ARG, "%s: alignment (16 bytes; ldx / ldw multiples of 8)", fn);
+  DecRowsArgs p{x, ldx, Wqkv, ldw, q_out, ldq, norm_w, eps, nullptr, 0, (H + 2 * Hkv) * D, K, B, 1, 1,
+                rope_cs, pos, k_slots, v_slots, slot_stride, row0, slot_rows, H, Hkv};
+  hipStream_t st = (hipStream_t)stream;
+  return K == 4096 ? launch_rows_nb<bf16_t, false, 2, 64, KV>(p, st) : launch_rows_nb<bf16_t, false, 1, 64, KV>(p, st);
+}
+
 extern "C" int vg_decode_qkv_rope_rows(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out,
                                        int64_t ldq, void* k_slots, void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* rope_cs,
                                        const int* pos, int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream) {
-  VG_CHECK(x && Wqkv && q_out && k_slots && v_slots && rope_cs && pos && B >= 1 && B <= 16 && slot_rows > 0, VG_ERR_ARG,
-           "vg_decode_qkv_rope_rows: bad args B=%d slot_rows=%d", B, slot_rows);
-  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
-           "vg_decode_qkv_rope_rows: H=%d Hkv=%d D=%d K=%d dtype=%d not covered", H, Hkv, D, K, dtype);
-  VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)Wqkv) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
-           "vg_decode_qkv_rope_rows: alignment (16 bytes; ldx / ldw multiples of 8)");
-  DecRowsArgs p{x, ldx, Wqkv, ldw, q_out, ldq, norm_w, eps, nullptr, 0, (H + 2 * Hkv) * D, K, B, 1, 1,
-                rope_cs, pos, k_slots, v_slots, slot_stride, row0, slot_rows, H, Hkv};
-  hipStream_t st = (hipStream_t)stream;
-  return K == 4096 ? launch_rows_nb<bf16_t, false, 2, 64>(p, st) : launch_rows_nb<bf16_t, false, 1, 64>(p, st);
+  return decode_qkv_rope_rows<bf16_t>("vg_decode_qkv_rope_rows", x, ldx, Wqkv, ldw, norm_w, eps, q_out, ldq, k_slots, v_slots, slot_stride, row0,
+                                      slot_rows, rope_cs, pos, H, Hkv, D, K, B, dtype, stream);
 }
 
-// vg_decode_qkv_rope_rows with e4m3 slots: slot_stride in elements = bytes (a multiple of 8, as the attention's loads need)
 extern "C" int vg_decode_qkv_rope_rows_kv8(const void* x, int64_t ldx, const void* Wqkv, int64_t ldw, const float* norm_w, float eps, void* q_out,
                                            int64_t ldq, uint8_t* k_slots, uint8_t* v_slots, int64_t slot_stride, int row0, int slot_rows,
                                            const float* rope_cs, const int* pos, int H, int Hkv, int D, int K, int B, int dtype, vg_stream_t stream) {
-  VG_CHECK(x && Wqkv && q_out && k_slots && v_slots && rope_cs && pos && B >= 1 && B <= 16 && slot_rows > 0, VG_ERR_ARG,
-           "vg_decode_qkv_rope_rows_kv8: bad args B=%d slot_rows=%d", B, slot_rows);
-  VG_CHECK(dtype == VG_BF16 && vg_decode_qkv_rope_supported(H, Hkv, D, K, dtype), VG_ERR_UNSUPPORTED,
-           "vg_decode_qkv_rope_rows_kv8: H=%d Hkv=%d D=%d K=%d dtype=%d not covered", H, Hkv, D, K, dtype);
-  VG_CHECK(ldw % 8 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)Wqkv) | ((uintptr_t)norm_w)) & 15) == 0 && slot_stride % 8 == 0 &&
-               slot_stride >= (int64_t)slot_rows * Hkv * D, VG_ERR_ARG,
-           "vg_decode_qkv_rope_rows_kv8: alignment (16 bytes; ldx / ldw / slot_stride multiples of 8; slots must not overlap)");
-  DecRowsArgs p{x, ldx, Wqkv, ldw, q_out, ldq, norm_w, eps, nullptr, 0, (H + 2 * Hkv) * D, K, B, 1, 1,
-                rope_cs, pos, k_slots, v_slots, slot_stride, row0, slot_rows, H, Hkv};
-  hipStream_t st = (hipStream_t)stream;
-  return K == 4096 ? launch_rows_nb<bf16_t, false, 2, 64, kv8_t>(p, st) : launch_rows_nb<bf16_t, false, 1, 64, kv8_t>(p, st);
+  return decode_qkv_rope_rows<kv8_t>("vg_decode_qkv_rope_rows_kv8", x, ldx, Wqkv, ldw, norm_w, eps, q_out, ldq, k_slots, v_slots, slot_stride, row0,
+                                     slot_rows, rope_cs, pos, H, Hkv, D, K, B, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1221,17 +1187,12 @@ static int launch_w8_rows_b(DecRowsW8Args p, hipStream_t st) {
   // x staging: the whole row when it fits the budget (always with the norm), else phases of batches with one pair per wave
   int nph = NB;
   if (!p.nw && (int64_t)BR * NB * BBYTES > DEC_ROWS_LDS) nph = max(1, DEC_ROWS_LDS / (BR * BBYTES));
-  int ppw = (npair + 2047) / 2048;                  // ~2 workgroups per CU, as vg_decode_gemv_rows
-  ppw = nph < NB ? 1 : min(ppw, DEC_ROWS_PPW);
+  const auto [ppw, blocks] = dec_rows_split(npair, nph < NB, DEC_ROWS_PPW);
   p.nph = nph;
   p.ppw = ppw;
   const size_t lds = (size_t)BR * nph * BBYTES;
-  static size_t cap = 64 * 1024;
-  if (lds > 64 * 1024 && lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_gemv_w8_rows_kernel<TO, GLU, NB, CPB, BR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cap = lds;
-  }
-  decode_gemv_w8_rows_kernel<TO, GLU, NB, CPB, BR><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
+  vg_raise_lds_cap<decode_gemv_w8_rows_kernel<TO, GLU, NB, CPB, BR>>(lds);
+  decode_gemv_w8_rows_kernel<TO, GLU, NB, CPB, BR><<<blocks, 256, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
@@ -1252,23 +1213,19 @@ static int launch_w8_rows_k(DecRowsW8Args p, hipStream_t st) {
 
 template <typename TO, bool GLU>
 static int launch_w8_rows(DecRowsW8Args p, hipStream_t st) {
-  if (p.B <= 1) return launch_w8_rows_k<TO, GLU, 1>(p, st);
-  if (p.B <= 2) return launch_w8_rows_k<TO, GLU, 2>(p, st);
-  if (p.B <= 4) return launch_w8_rows_k<TO, GLU, 4>(p, st);
-  if (p.B <= 8) return launch_w8_rows_k<TO, GLU, 8>(p, st);
-  return launch_w8_rows_k<TO, GLU, 16>(p, st);
+  return dec_with_bucket(p.B, [&](auto br) { return launch_w8_rows_k<TO, GLU, decltype(br)::value>(p, st); });
 }
 
 extern "C" int vg_decode_gemv_w8_rows(const void* x, int64_t ldx, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, int64_t ldy,
                                       const float* norm_w, float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype,
                                       vg_stream_t stream) {
-  VG_CHECK(x && W8 && wscale && y && N > 0 && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemv_w8_rows: bad args N=%d B=%d", N, B);
+  VG_CHECK(x && W8 && wscale && y && N > 0 && dec_rows_b_ok(B), VG_ERR_ARG, "vg_decode_gemv_w8_rows: bad args N=%d B=%d", N, B);
   VG_CHECK(vg_decode_gemv_w8_rows_supported(K), VG_ERR_UNSUPPORTED,
            "vg_decode_gemv_w8_rows: K=%d is not one of the supported row lengths (3072, 4096, 8192, 14336)", K);
   VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemv_w8_rows: bad out_dtype %d", out_dtype);
   VG_CHECK(ldw % 16 == 0 && ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)W8) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
            "vg_decode_gemv_w8_rows: alignment (16 bytes; ldx a multiple of 8, ldw of 16)");
-  const int br = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;      // the bucket the kernel stages
+  const int br = dec_bucket(B);      // the bucket the kernel stages
   VG_CHECK(!norm_w || (int64_t)br * K * 2 <= 160 * 1024 - 8 * 1024, VG_ERR_UNSUPPORTED,
            "vg_decode_gemv_w8_rows: the norm stages the whole rows of the %d-row bucket: B=%d K=%d do not fit", br, B, K);
   DecRowsW8Args p{x, ldx, W8, ldw, wscale, y, ldy, norm_w, eps, R, ldr, N, K, B, 1, 1};
@@ -1626,11 +1583,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecAttnArgs p) {
 
 template <typename T, int G, int DT, int LB = 1, typename KV = T>
 static void launch_decode_attn_gd(const DecAttnArgs& p, dim3 grid, size_t lds, hipStream_t st) {
-  static size_t lds_cap = 64 * 1024;   // raise the dynamic-LDS cap only when a shape needs it (never inside a replay)
-  if (lds > lds_cap) {
-    (void)hipFuncSetAttribute((const void*)decode_attn_kernel<T, G, DT, LB, KV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    lds_cap = lds;
-  }
+  vg_raise_lds_cap<decode_attn_kernel<T, G, DT, LB, KV>>(lds);
   decode_attn_kernel<T, G, DT, LB, KV><<<grid, 256, lds, st>>>(p);
 }
 
@@ -1676,27 +1629,6 @@ extern "C" int64_t vg_decode_attention_ws_floats(int H, int Hkv, int D, int max_
   return (int64_t)Hkv * nsplit * (H / Hkv) * (D + 2) + Hkv;
 }
 
-extern "C" int vg_decode_attention(const void* qkv, void* k_cache, void* v_cache, const float* cos, const float* sin,
-                                   void* out, int H, int Hkv, int D, int max_len, int window, float scale, const int* pos_dev,
-                                   float* workspace, int64_t ws_floats, int keys_per_wg, int dtype, vg_stream_t stream) {
-  VG_CHECK(qkv && k_cache && v_cache && cos && sin && out && pos_dev && workspace, VG_ERR_ARG, "vg_decode_attention: null pointer");
-  VG_CHECK(keys_per_wg == 0 || keys_per_wg == 64 || keys_per_wg == 128, VG_ERR_ARG, "vg_decode_attention: keys_per_wg %d not in {0, 64, 128}", keys_per_wg);
-  VG_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && D > 0 && D % 2 == 0 && max_len > 0, VG_ERR_ARG,
-           "vg_decode_attention: bad shape H=%d Hkv=%d D=%d max_len=%d", H, Hkv, D, max_len);
-  VG_CHECK(dtype == VG_BF16 || dtype == VG_F32, VG_ERR_ARG, "vg_decode_attention: bad dtype %d", dtype);
-  VG_CHECK(window >= 0, VG_ERR_ARG, "vg_decode_attention: window %d < 0", window);
-  const int kpc = dtype == VG_BF16 ? 8 : 4, es = dtype == VG_BF16 ? 2 : 4;
-  VG_CHECK(D % kpc == 0 && D * es <= 512, VG_ERR_UNSUPPORTED, "vg_decode_attention: head_dim %d unsupported (multiple of %d, <= %d)", D, kpc, 512 / es);
-  VG_CHECK((((uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0, VG_ERR_ARG, "vg_decode_attention: caches must be 16-byte aligned");
-  const int64_t need = vg_decode_attention_ws_floats(H, Hkv, D, max_len);
-  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
-  const int nsplit = (max_len + 63) / 64;
-  VG_CHECK(nsplit <= 128, VG_ERR_UNSUPPORTED, "vg_decode_attention: max_len %d > 8192", max_len);
-  DecAttnArgs p{qkv, k_cache, v_cache, cos, sin, out, workspace, (int*)(workspace + (need - Hkv)), pos_dev, H, Hkv, D, nsplit, scale, window};
-  if (dtype == VG_BF16) return launch_decode_attn<bf16_t>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
-  return launch_decode_attn<float>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
-}
-
 // vg_decode_attention on e4m3 caches (kv8_t above): bf16 qkv / out, the same workspace, the same shapes
 extern "C" int vg_decode_attention_kv8_supported(int H, int Hkv, int D, int dtype) {
   if (dtype != VG_BF16 || H <= 0 || Hkv <= 0 || H % Hkv || D <= 0 || D % 8 || D > 256) return 0;
@@ -1704,22 +1636,54 @@ extern "C" int vg_decode_attention_kv8_supported(int H, int Hkv, int D, int dtyp
   return G == 1 || G == 2 || G == 4 || G == 8;
 }
 
+// fn: the entry point's name for the messages.  KV: the caches' element type — void = the activation dtype, kv8_t = e4m3 codes.  The caches'
+// alignment is one chunk of that type (16 bytes, 8 bytes of e4m3 codes); what each entry point covers is checked in its own words
+template <typename KV>
+static int decode_attention(const char* fn, const void* qkv, void* k_cache, void* v_cache, const float* cos, const float* sin, void* out, int H, int Hkv,
+                            int D, int max_len, int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats, int keys_per_wg,
+                            int dtype, vg_stream_t stream) {
+  constexpr bool KV8 = std::is_same<KV, kv8_t>::value;
+  constexpr int KVA = KV8 ? 8 : 16;
+  VG_CHECK(qkv && k_cache && v_cache && cos && sin && out && pos_dev && workspace, VG_ERR_ARG, "%s: null pointer", fn);
+  VG_CHECK(keys_per_wg == 0 || keys_per_wg == 64 || keys_per_wg == 128, VG_ERR_ARG, "%s: keys_per_wg %d not in {0, 64, 128}", fn, keys_per_wg);
+  if constexpr (KV8) {
+    VG_CHECK(max_len > 0 && window >= 0, VG_ERR_ARG, "%s: bad max_len %d / window %d", fn, max_len, window);
+    VG_CHECK(vg_decode_attention_kv8_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED,
+             "%s: H=%d Hkv=%d D=%d dtype=%d not covered (bf16, H/Hkv in {1,2,4,8}, head_dim a multiple of 8, <= 256)", fn, H, Hkv, D, dtype);
+  } else {
+    VG_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && D > 0 && D % 2 == 0 && max_len > 0, VG_ERR_ARG, "%s: bad shape H=%d Hkv=%d D=%d max_len=%d", fn, H, Hkv,
+             D, max_len);
+    VG_CHECK(dtype == VG_BF16 || dtype == VG_F32, VG_ERR_ARG, "%s: bad dtype %d", fn, dtype);
+    VG_CHECK(window >= 0, VG_ERR_ARG, "%s: window %d < 0", fn, window);
+    const int kpc = dtype == VG_BF16 ? 8 : 4, es = dtype == VG_BF16 ? 2 : 4;
+    VG_CHECK(D % kpc == 0 && D * es <= 512, VG_ERR_UNSUPPORTED, "%s: head_dim %d unsupported (multiple of %d, <= %d)", fn, D, kpc, 512 / es);
+  }
+  VG_CHECK((((uintptr_t)k_cache | (uintptr_t)v_cache) & (KVA - 1)) == 0, VG_ERR_ARG, "%s: caches must be %d-byte aligned", fn, KVA);
+  const int64_t need = vg_decode_attention_ws_floats(H, Hkv, D, max_len);
+  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "%s: workspace %lld < %lld floats", fn, (long long)ws_floats, (long long)need);
+  const int nsplit = (max_len + 63) / 64;
+  VG_CHECK(nsplit <= 128, VG_ERR_UNSUPPORTED, "%s: max_len %d > 8192", fn, max_len);
+  DecAttnArgs p{qkv, k_cache, v_cache, cos, sin, out, workspace, (int*)(workspace + (need - Hkv)), pos_dev, H, Hkv, D, nsplit, scale, window};
+  if constexpr (KV8) {
+    return launch_decode_attn<bf16_t, kv8_t>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
+  } else {
+    if (dtype == VG_BF16) return launch_decode_attn<bf16_t>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
+    return launch_decode_attn<float>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
+  }
+}
+
+extern "C" int vg_decode_attention(const void* qkv, void* k_cache, void* v_cache, const float* cos, const float* sin,
+                                   void* out, int H, int Hkv, int D, int max_len, int window, float scale, const int* pos_dev,
+                                   float* workspace, int64_t ws_floats, int keys_per_wg, int dtype, vg_stream_t stream) {
+  return decode_attention<void>("vg_decode_attention", qkv, k_cache, v_cache, cos, sin, out, H, Hkv, D, max_len, window, scale, pos_dev, workspace,
+                                ws_floats, keys_per_wg, dtype, stream);
+}
+
 extern "C" int vg_decode_attention_kv8(const void* qkv, void* k_cache, void* v_cache, const float* cos, const float* sin, void* out, int H, int Hkv,
                                        int D, int max_len, int window, float scale, const int* pos_dev, float* workspace, int64_t ws_floats,
                                        int keys_per_wg, int dtype, vg_stream_t stream) {
-  VG_CHECK(qkv && k_cache && v_cache && cos && sin && out && pos_dev && workspace, VG_ERR_ARG, "vg_decode_attention_kv8: null pointer");
-  VG_CHECK(keys_per_wg == 0 || keys_per_wg == 64 || keys_per_wg == 128, VG_ERR_ARG, "vg_decode_attention_kv8: keys_per_wg %d not in {0, 64, 128}",
-           keys_per_wg);
-  VG_CHECK(max_len > 0 && window >= 0, VG_ERR_ARG, "vg_decode_attention_kv8: bad max_len %d / window %d", max_len, window);
-  VG_CHECK(vg_decode_attention_kv8_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED,
-           "vg_decode_attention_kv8: H=%d Hkv=%d D=%d dtype=%d not covered (bf16, H/Hkv in {1,2,4,8}, head_dim a multiple of 8, <= 256)", H, Hkv, D, dtype);
-  VG_CHECK((((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) == 0, VG_ERR_ARG, "vg_decode_attention_kv8: caches must be 8-byte aligned");
-  const int64_t need = vg_decode_attention_ws_floats(H, Hkv, D, max_len);
-  VG_CHECK(ws_floats >= need, VG_ERR_ARG, "vg_decode_attention_kv8: workspace %lld < %lld floats", (long long)ws_floats, (long long)need);
-  const int nsplit = (max_len + 63) / 64;
-  VG_CHECK(nsplit <= 128, VG_ERR_UNSUPPORTED, "vg_decode_attention_kv8: max_len %d > 8192", max_len);
-  DecAttnArgs p{qkv, k_cache, v_cache, cos, sin, out, workspace, (int*)(workspace + (need - Hkv)), pos_dev, H, Hkv, D, nsplit, scale, window};
-  return launch_decode_attn<bf16_t, kv8_t>(p, H / Hkv, keys_per_wg, (hipStream_t)stream);
+  return decode_attention<kv8_t>("vg_decode_attention_kv8", qkv, k_cache, v_cache, cos, sin, out, H, Hkv, D, max_len, window, scale, pos_dev, workspace,
+                                 ws_floats, keys_per_wg, dtype, stream);
 }
 
 // dst[i] = e4m3(src[i]) (kv8_pack4: clamp, round to nearest even, no scale) for n elements: a prefill's bf16 K / V rows -> the e4m3 cache
@@ -1802,7 +1766,7 @@ static int decode_attention_rows_impl(const void* qkv, int64_t ldqkv, const void
                                       void* v_slots, int64_t slot_stride, int row0, int slot_rows, const float* cos, const float* sin, void* out,
                                       int H, int Hkv, int D, int n_bound, int window, float scale, const int* pos, int kpw_min, float* workspace,
                                       int64_t ws_floats, int B, int dtype, bool kv8, vg_stream_t stream) {
-  VG_CHECK(qkv && k_cache && v_cache && k_slots && v_slots && cos && sin && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG,
+  VG_CHECK(qkv && k_cache && v_cache && k_slots && v_slots && cos && sin && out && pos && workspace && dec_rows_b_ok(B), VG_ERR_ARG,
            "vg_decode_attention_rows: bad args B=%d", B);
   VG_CHECK(vg_decode_attention_rows_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "vg_decode_attention_rows: H=%d Hkv=%d D=%d dtype=%d not covered",
            H, Hkv, D, dtype);
@@ -2093,17 +2057,6 @@ __global__ __launch_bounds__(256, 2) void decode_layer_kernel(DecLayerArgs q) {
   }
 }
 
-static int dec_role_blocks(int npair, int* ppw_out) {     // launch_decode_gemv's split
-  constexpr int bpc = 2;
-  const int maxw = 256 * bpc * 4;
-  int ppw = (npair + maxw - 1) / maxw;
-  for (int c = ppw; c <= 2 * ppw; ++c)
-    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
-  if (ppw > DEC_MAX_PPW) ppw = DEC_MAX_PPW;
-  *ppw_out = ppw;
-  return (npair + 4 * ppw - 1) / (4 * ppw);
-}
-
 // 0: not available for this shape; 1: attention + o_proj; 3: + the MLP roles
 extern "C" int vg_decode_layer_roles(int H, int Hkv, int D, int hidden, int inter, int dtype) {
   if (H <= 0 || Hkv <= 0 || H % Hkv || (int64_t)H * D != hidden) return 0;
@@ -2116,11 +2069,7 @@ extern "C" int64_t vg_decode_layer_flag_ints(void) { return DEC_CHAIN_INTS; }
 
 template <typename T, int G, int DT, int NBH, int CPBH, int NBI>
 static int launch_decode_layer(const DecLayerArgs& q, int blocks, size_t lds, hipStream_t st) {
-  static size_t lds_cap = 64 * 1024;
-  if (lds > lds_cap) {
-    (void)hipFuncSetAttribute((const void*)decode_layer_kernel<T, G, DT, NBH, CPBH, NBI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    lds_cap = lds;
-  }
+  vg_raise_lds_cap<decode_layer_kernel<T, G, DT, NBH, CPBH, NBI>>(lds);
   decode_layer_kernel<T, G, DT, NBH, CPBH, NBI><<<blocks, 256, lds, st>>>(q);
   VG_LAUNCH_CHECK();
   return VG_OK;
@@ -2151,15 +2100,16 @@ extern "C" int vg_decode_layer(const void* qkv, void* k_cache, void* v_cache, co
   q.a = DecAttnArgs{qkv, k_cache, v_cache, cos, sin, attn_out, workspace, (int*)(workspace + (need - Hkv)), pos_dev, H, Hkv, D, nsplit, scale, window};
   q.flags = flags;
   q.nroles = want;
-  int ppw = 1;
-  q.r[0].nblocks = dec_role_blocks((hidden + 1) / 2, &ppw);
-  q.r[0].g = DecGemvArgs{attn_out, Wo, y_o, nullptr, resid, hidden, hidden, ldo, 0.f, ppw, nullptr};
+  const DecSplit so = dec_pair_split((hidden + 1) / 2, 2, DEC_MAX_PPW);      // o and down: N = hidden
+  q.r[0].nblocks = so.blocks;
+  q.r[0].g = DecGemvArgs{attn_out, Wo, y_o, nullptr, resid, hidden, hidden, ldo, 0.f, so.ppw, nullptr};
   int blocks = nsplit * Hkv + q.r[0].nblocks;
   if (want == 3) {
-    q.r[1].nblocks = dec_role_blocks(inter, &ppw);
-    q.r[1].g = DecGemvArgs{y_o, Wgu, act, norm_w, nullptr, inter, hidden, ldgu, eps, ppw, nullptr};
-    q.r[2].nblocks = dec_role_blocks((hidden + 1) / 2, &ppw);
-    q.r[2].g = DecGemvArgs{act, Wdown, y, nullptr, y_o, hidden, inter, lddown, 0.f, ppw, nullptr};
+    const DecSplit sgu = dec_pair_split(inter, 2, DEC_MAX_PPW);              // gate|up (GLU): inter pairs
+    q.r[1].nblocks = sgu.blocks;
+    q.r[1].g = DecGemvArgs{y_o, Wgu, act, norm_w, nullptr, inter, hidden, ldgu, eps, sgu.ppw, nullptr};
+    q.r[2].nblocks = so.blocks;
+    q.r[2].g = DecGemvArgs{act, Wdown, y, nullptr, y_o, hidden, inter, lddown, 0.f, so.ppw, nullptr};
     blocks += q.r[1].nblocks + q.r[2].nblocks;
   }
   const int G = H / Hkv, KP = 256 / (D / kpc);

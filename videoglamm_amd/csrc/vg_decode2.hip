@@ -17,6 +17,7 @@
 // vg_decode_advance: what the host did between two steps — apply a forced token, record the emitted and the raw token, bump the position —
 // so that step k + 1 can be enqueued before token k has been read back; and the current position's cos / sin row for vg_decode_qkv_rope.
 #include "vg_common.h"
+#include "vg_decode_launch.h"
 
 template <int CTRL> __device__ __forceinline__ float dec_dpp(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
@@ -267,11 +268,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn2_kernel(DecAttn2Args p) {
 template <int G, int NW, bool ROWS, typename KV>
 static int launch_attn2(const DecAttn2Args& p, hipStream_t st, int B = 1) {
   const size_t lds = sizeof(float) * ((size_t)NW * 4 * G * A2_D + NW * G * 2);
-  static size_t cap = 64 * 1024;
-  if (lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_attn2_kernel<G, NW, ROWS, KV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cap = lds;
-  }
+  vg_raise_lds_cap<decode_attn2_kernel<G, NW, ROWS, KV>>(lds);
   decode_attn2_kernel<G, NW, ROWS, KV><<<dim3(p.nsplit, p.Hkv, B), NW * 64, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
@@ -348,7 +345,7 @@ static int decode_attention2_rows(const char* fn, const void* q, const void* k_c
                                   int64_t slot_stride, int row0, int slot_rows, void* out, int H, int Hkv, int D, int n_bound, int window, float scale,
                                   const int* pos, float* workspace, int64_t ws_floats, int keys_per_wg, int B, int dtype, vg_stream_t stream) {
   constexpr int KVA = 8 * (int)sizeof(KV);
-  VG_CHECK(q && k_cache && v_cache && k_slots && v_slots && out && pos && workspace && B >= 1 && B <= 16, VG_ERR_ARG, "%s: bad args", fn);
+  VG_CHECK(q && k_cache && v_cache && k_slots && v_slots && out && pos && workspace && dec_rows_b_ok(B), VG_ERR_ARG, "%s: bad args", fn);
   VG_CHECK(vg_decode_attention2_supported(H, Hkv, D, dtype), VG_ERR_UNSUPPORTED, "%s: H=%d Hkv=%d D=%d dtype=%d not covered", fn, H, Hkv, D, dtype);
   VG_CHECK(keys_per_wg == 128 || keys_per_wg == 256, VG_ERR_ARG, "%s: keys_per_wg %d not in {128, 256}", fn, keys_per_wg);
   VG_CHECK(row0 >= 0 && row0 % keys_per_wg == 0 && row0 <= max_len && slot_rows > 0 && n_bound > row0 && n_bound <= row0 + slot_rows && window >= 0, VG_ERR_ARG,

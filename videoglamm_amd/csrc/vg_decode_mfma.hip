@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "vg_common.h"
+#include "vg_decode_launch.h"
 
 namespace {
 
@@ -326,7 +327,7 @@ extern "C" int vg_decode_gemm_rows_supported(int N, int K) { return gr_shape(N, 
 
 extern "C" int vg_decode_gemm_rows(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, const float* norm_w, float eps,
                                    const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream) {
-  VG_CHECK(x && W && y && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemm_rows: bad args B=%d", B);
+  VG_CHECK(x && W && y && dec_rows_b_ok(B), VG_ERR_ARG, "vg_decode_gemm_rows: bad args B=%d", B);
   VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemm_rows: out_dtype %d (bf16 or fp32)", out_dtype);
   VG_CHECK(vg_decode_gemm_rows_supported(N, K), VG_ERR_UNSUPPORTED,
            "vg_decode_gemm_rows: K one of 3072, 4096, 8192, 14336 only (N=%d K=%d)", N, K);
@@ -342,7 +343,7 @@ extern "C" int vg_decode_gemm_w8_rows_supported(int N, int K) { return gr_shape(
 extern "C" int vg_decode_gemm_w8_rows(const void* x, int64_t ldx, const uint8_t* W8, int64_t ldw, const float* wscale, void* y, int64_t ldy,
                                       const float* norm_w, float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype,
                                       vg_stream_t stream) {
-  VG_CHECK(x && W8 && wscale && y && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemm_w8_rows: bad args B=%d", B);
+  VG_CHECK(x && W8 && wscale && y && dec_rows_b_ok(B), VG_ERR_ARG, "vg_decode_gemm_w8_rows: bad args B=%d", B);
   VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemm_w8_rows: out_dtype %d (bf16 or fp32)", out_dtype);
   VG_CHECK(gr_shape(N, K), VG_ERR_UNSUPPORTED, "vg_decode_gemm_w8_rows: K one of 3072, 4096, 8192, 14336 only (N=%d K=%d)", N, K);
   VG_CHECK(ldw % 16 == 0 && ldx % 8 == 0 && ldw >= K && ((((uintptr_t)x) | ((uintptr_t)W8) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
@@ -356,7 +357,7 @@ extern "C" int vg_decode_gemm_w4_rows_supported(int N, int K) { return gr_shape(
 
 extern "C" int vg_decode_gemm_w4_rows(const void* x, int64_t ldx, const uint8_t* W4, int64_t ldw_bytes, void* y, int64_t ldy, const float* norm_w,
                                       float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream) {
-  VG_CHECK(x && W4 && y && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemm_w4_rows: bad args B=%d", B);
+  VG_CHECK(x && W4 && y && dec_rows_b_ok(B), VG_ERR_ARG, "vg_decode_gemm_w4_rows: bad args B=%d", B);
   VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemm_w4_rows: out_dtype %d (bf16 or fp32)", out_dtype);
   VG_CHECK(gr_shape(N, K), VG_ERR_UNSUPPORTED, "vg_decode_gemm_w4_rows: K one of 3072, 4096, 8192, 14336 only (N=%d K=%d)", N, K);
   const int head = 64 * (K <= 4096 ? 2 : K == 8192 ? 4 : 8);      // SPL scale bytes per lane: the packed rows of vg_decode_gemv_w4

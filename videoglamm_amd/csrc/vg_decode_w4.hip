@@ -13,6 +13,7 @@
 // that a lane's SPL scales are ONE 2 / 4 / 8-byte load (packed rows, scales == NULL), or a second array in the logical order read with one byte load per
 // chunk (the 64 lanes of a wave cover one 64-byte line).
 #include "vg_common.h"
+#include "vg_decode_launch.h"
 #include <type_traits>
 
 struct DecW4Args {
@@ -232,14 +233,7 @@ static int64_t dec4_row_bytes(int K) { return 64 * dec4_spl(K) + K / 2; }     //
 
 template <typename TO, bool GLU, bool SEP>
 static int launch_decode_gemv_w4(DecW4Args p, hipStream_t st) {
-  const int bpc = 4;                                   // workgroups per CU the row pairs are spread over, as vg_decode_gemv_w8
-  const int npair = GLU ? p.N : (p.N + 1) / 2;
-  const int maxw = 256 * bpc * 4;
-  int ppw = (npair + maxw - 1) / maxw;                 // row pairs per wave
-  for (int c = ppw; c <= 2 * ppw; ++c)                 // prefer whole rounds of 256 workgroups
-    if (((npair + 4 * c - 1) / (4 * c)) % 256 == 0 && npair % (4 * c) == 0) { ppw = c; break; }
-  if (ppw > DEC4_MAX_PPW) ppw = DEC4_MAX_PPW;
-  const int blocks = (npair + 4 * ppw - 1) / (4 * ppw);
+  const auto [ppw, blocks] = dec_pair_split(GLU ? p.N : (p.N + 1) / 2, 4, DEC4_MAX_PPW);      // four workgroups per CU, as vg_decode_gemv_w8
   p.ppw = ppw;
   const size_t lds = (size_t)p.K * 2;
   switch (p.K) {
@@ -506,17 +500,11 @@ extern "C" int vg_decode_gemv_w4_rows_supported(int K) { return dec4_spl(K) != 0
 template <bool GLU, int NWC, int BR, int UPP>
 static int launch_w4_rows_u(DecW4RowsArgs p, hipStream_t st) {
   constexpr int CPL = Dec4Shape<NWC>::CPL;
-  const int npair = GLU ? p.N : (p.N + 1) / 2;
-  int ppw = (npair + 2047) / 2048;                  // ~2 workgroups per CU, as vg_decode_gemv_w8_rows
-  ppw = UPP < CPL ? 1 : min(ppw, DEC4_ROWS_PPW);
+  const auto [ppw, blocks] = dec_rows_split(GLU ? p.N : (p.N + 1) / 2, UPP < CPL, DEC4_ROWS_PPW);
   p.ppw = ppw;
   const size_t lds = (size_t)BR * 4 * (UPP == CPL ? NWC : UPP * 64) * 16;
-  static size_t cap = 64 * 1024;
-  if (lds > 64 * 1024 && lds > cap) {
-    (void)hipFuncSetAttribute((const void*)decode_gemv_w4_rows_kernel<GLU, NWC, BR, UPP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cap = lds;
-  }
-  decode_gemv_w4_rows_kernel<GLU, NWC, BR, UPP><<<(npair + 4 * ppw - 1) / (4 * ppw), 256, lds, st>>>(p);
+  vg_raise_lds_cap<decode_gemv_w4_rows_kernel<GLU, NWC, BR, UPP>>(lds);
+  decode_gemv_w4_rows_kernel<GLU, NWC, BR, UPP><<<blocks, 256, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
@@ -551,16 +539,12 @@ static int launch_w4_rows_k(DecW4RowsArgs p, hipStream_t st) {
 
 template <bool GLU>
 static int launch_w4_rows(DecW4RowsArgs p, hipStream_t st) {
-  if (p.B <= 1) return launch_w4_rows_k<GLU, 1>(p, st);
-  if (p.B <= 2) return launch_w4_rows_k<GLU, 2>(p, st);
-  if (p.B <= 4) return launch_w4_rows_k<GLU, 4>(p, st);
-  if (p.B <= 8) return launch_w4_rows_k<GLU, 8>(p, st);
-  return launch_w4_rows_k<GLU, 16>(p, st);
+  return dec_with_bucket(p.B, [&](auto br) { return launch_w4_rows_k<GLU, decltype(br)::value>(p, st); });
 }
 
 extern "C" int vg_decode_gemv_w4_rows(const void* x, int64_t ldx, const uint8_t* W4, int64_t ldw_bytes, void* y, int64_t ldy, const float* norm_w,
                                       float eps, const void* R, int64_t ldr, int N, int K, int B, int glu, int out_dtype, vg_stream_t stream) {
-  VG_CHECK(x && W4 && y && N > 0 && B >= 1 && B <= 16, VG_ERR_ARG, "vg_decode_gemv_w4_rows: bad args N=%d B=%d", N, B);
+  VG_CHECK(x && W4 && y && N > 0 && dec_rows_b_ok(B), VG_ERR_ARG, "vg_decode_gemv_w4_rows: bad args N=%d B=%d", N, B);
   VG_CHECK(vg_decode_gemv_w4_rows_supported(K), VG_ERR_UNSUPPORTED,
            "vg_decode_gemv_w4_rows: K=%d is not one of the supported row lengths (3072, 4096, 8192, 14336)", K);
   VG_CHECK(out_dtype == VG_BF16 || out_dtype == VG_F32, VG_ERR_ARG, "vg_decode_gemv_w4_rows: bad out_dtype %d", out_dtype);
@@ -569,7 +553,7 @@ extern "C" int vg_decode_gemv_w4_rows(const void* x, int64_t ldx, const uint8_t*
            (long long)dec4_row_bytes(K), K);
   VG_CHECK(ldx % 8 == 0 && ((((uintptr_t)x) | ((uintptr_t)W4) | ((uintptr_t)norm_w)) & 15) == 0, VG_ERR_ARG,
            "vg_decode_gemv_w4_rows: alignment (16 bytes; ldx a multiple of 8)");
-  const int br = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;      // the bucket the kernel stages
+  const int br = dec_bucket(B);      // the bucket the kernel stages
   VG_CHECK(!norm_w || (int64_t)br * K * 2 <= 160 * 1024 - 8 * 1024, VG_ERR_UNSUPPORTED,
            "vg_decode_gemv_w4_rows: the norm stages the whole rows of the %d-row bucket: B=%d K=%d do not fit", br, B, K);
   DecW4RowsArgs p{x, ldx, W4, ldw_bytes, y, ldy, norm_w, eps, R, ldr, N, K, B, 1, out_dtype == VG_F32};

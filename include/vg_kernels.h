@@ -621,9 +621,18 @@ int vg_gemm_f8(const uint8_t* A8, int64_t lda, const float* a_scale, const uint8
 int vg_gemm_w4a8_supported(int64_t N, int64_t K);
 int vg_gemm_w4a8(const uint8_t* A8, int64_t lda, const float* a_scale, const uint8_t* W4, int64_t ldw_bytes, void* C, int64_t ldc,
                  const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int out_dtype, int a_op, vg_stream_t stream);
-/* Which kernel an (M, N, K) GEMM of vg_gemm / vg_gemm_window is routed to with the current knobs (measurement aid:
- * bench.py attributes per-launch times to kernels with it): 0 gemm_skinny_kernel (M <= 16), 1 gemm_tile_glds_kernel,
- * 2 gemm_tile_k64b_kernel, 3 gemm_tile_w128_kernel, 4 gemm_tile_s128_kernel.  N = output columns (F for a_op == 1).
+/* Which kernel an (M, N, K) GEMM of vg_gemm / vg_gemm_window / vg_gemm_ln is routed to with the current knobs (VG_GEMM_RR, VG_GEMM_P8).  bench.py
+ * attributes per-launch times to kernels with it, ops.linear decides its tail split and ops.linear_ln its fused form:
+ *   0 gemm_skinny_kernel (M <= 16), 1 gemm_tile_glds_kernel (128x128 tiles, LDS-DMA; its SwiGLU tile form included), 2 gemm_tile_k64b_kernel,
+ *   3 gemm_tile_p8_kernel (256x256 tiles, phase-split), 4 gemm_tile_s128_kernel, 5 gemm_small64_kernel, 6 gemm_tile_p8n_kernel (256x192 tiles),
+ *   7 gemm_rr_kernel (row-register, K = 144 / 288).
+ * The answer is the launcher's own plan (gemm_plan, videoglamm_amd/csrc/vg_gemm_route.h) for the contiguous, 16-byte aligned, batch-1 call without an
+ * epilogue: lda = ldw = K, ldc = N, bf16 output for bf16 input and fp32 otherwise, no bias / activation / LayerScale / residual.  A call whose strides,
+ * alignment, epilogue or batch differ can be refused by a kernel the query names (vg_gemm_ln then returns VG_ERR_UNSUPPORTED; vg_gemm takes the next kernel
+ * of the plan).  N = output columns (F for a_op == 1).
+ * windowed != 0: a vg_gemm_window call whose geometry is unknown here, so no 256-row kernel takes its window form and the answer is one of 1, 2, 4, 7.  The
+ * launcher itself sends a padding-free gather or scatter of power-of-two windows to kernels 3 / 6 when the shape rules say so: for those calls the
+ * answer names the 128x128 kernel that would run otherwise.
  * Launches nothing. */
 int vg_gemm_route(int64_t M, int64_t N, int64_t K, int in_dtype, int a_op, int windowed);
 

@@ -1066,6 +1066,59 @@ def test_gemm_route_knobs(cuda):
     assert r.returncode == 0 and "knobs ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def _gemm_entry_state_sequence():
+    """runs in a child process with VG_GEMM_RR=2 (the row-register kernel on every eligible shape, so that a LayerNorm left behind by vg_gemm_ln would
+    be APPLIED by the plain call that follows)."""
+    from videoglamm_amd import _lib, ops
+    lib = _lib.load()
+    assert lib.vg_init(0) > 0
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(7)
+    ints = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).to(torch.bfloat16)          # integer-valued bf16: every product and sum is exact
+    # 1. a window gather
+    xw, ww = ints(-4, 4, 1, 8, 8, 64), ints(-1, 1, 64, 64)
+    yw = ops.linear_window(xw.to(dev), ww.to(dev), None, 1, 8, 8, 4, scatter=False)
+    want = xw.view(1, 2, 4, 2, 4, 64).permute(0, 1, 3, 2, 4, 5).reshape(4, 16, 64).float() @ ww.float().t()
+    assert want.abs().max() <= 256 and torch.equal(yw.float().cpu(), want)
+    # 2. a fused LayerNorm + projection on the row-register kernel
+    xl, wl = ints(-4, 4, 32, 144), ints(-1, 1, 16, 144)
+    plain = xl.float() @ wl.float().t()
+    assert plain.abs().max() <= 256
+    assert lib.vg_gemm_route(32, 16, 144, ops.BF16, 0, 0) == 7
+    ln = (torch.full((144,), 2.0, device=dev), torch.ones(144, device=dev), 1e-6)
+    yl = ops.linear_ln(xl.to(dev), ln, wl.to(dev))
+    assert torch.isfinite(yl).all() and not torch.equal(yl.float().cpu(), plain)
+    # 3. refused calls of both entry points
+    xd, wd, out = xl.to(dev), wl.to(dev), torch.empty(32, 16, dtype=torch.bfloat16, device=dev)
+    rc = lib.vg_gemm_ln(ops._p(xd), 144, ops._p(wd), 144, ops._p(out), 16, None, ops._p(ln[0]), ops._p(ln[1]), 1e-6, 32, 16, 144, 0, 0, 0, 0, 0, 0, None,
+                        ops.F32, ops._stream())
+    assert rc == -3 and lib.vg_last_error().decode().startswith("vg_gemm_ln: bf16 only")
+    rc = lib.vg_gemm_window(ops._p(xw.to(dev)), 64, ops._p(ww.to(dev)), 64, ops._p(yw), 64, None, None, None, 0, 64, 64, ops.BF16, ops.BF16, 0,
+                            1, 1, 8, 8, 0, ops._p(ops._zero_row(64, torch.bfloat16, dev)), ops._stream())
+    assert rc == -1 and lib.vg_last_error().decode().startswith("vg_gemm_window: bad window")
+    # 4. plain calls: no window, no LayerNorm
+    xp = xw.view(64, 64)[:32]
+    yp = ops.linear(xp.to(dev), ww.to(dev))
+    assert torch.equal(yp.float().cpu(), xp.float() @ ww.float().t())
+    assert torch.equal(ops.linear(xd, wd).float().cpu(), plain)
+    print("state ok")
+
+
+def test_gemm_entry_points_carry_no_state(cuda):
+    """vg_gemm_window and vg_gemm_ln hand their window and their LayerNorm to the shared body explicitly: nothing of a call — completed or refused —
+    is seen by the next one.  Integer-valued bf16 operands (|x| <= 4, weights in {-1, 0, 1}, sums <= 256): every plain result equals the fp32
+    product exactly."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path[:0] = [%r, %r]\n"
+            "import test_kernels_gpu as t\n"
+            "t._gemm_entry_state_sequence()\n") % (os.path.dirname(here), here)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, VG_GEMM_RR="2"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "state ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 WIN = [  # (Hq, Hkv, Sq, Skv, D, window): causal + sliding window (the query's own position and the window - 1 before it)
     (4, 4, 700, 700, 96, 100),       # Phi-3 head dim, window shorter than a query tile
     (4, 4, 700, 700, 96, 257),       # window spanning several key tiles, ragged edge

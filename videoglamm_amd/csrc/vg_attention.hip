@@ -581,11 +581,7 @@ static int launch_attn(const AttnArgs& p, hipStream_t st) {
   constexpr int lds = (BQ + BKV) * RS + vbytes + (DB ? BKV * RS + vbytes : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
   static_assert(KS == 1 || lds >= (NW / KS) * (DVP / 32 * 16 + 2) * 64 * 4, "the key-half merge reuses the tile buffers");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_kernel<T, DP, BKV, NW, KS, DVP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
+  vg_raise_lds_cap<attn_kernel<T, DP, BKV, NW, KS, DVP>>(lds);
   dim3 grid(((p.Sq + BQ - 1) / BQ) * p.nsplit, p.Hq, p.B);
   if (p.fold) grid = dim3(p.nsplit, p.Hkv, p.B);
   attn_kernel<T, DP, BKV, NW, KS, DVP><<<grid, NW * 64, lds, st>>>(p);
@@ -778,11 +774,7 @@ template <int D>
 static int launch_win256(const WinAttnArgs& p, hipStream_t st) {
   constexpr int CH = D / 8, RS = (CH | 1) * 16;
   constexpr int lds = 4 * D * 128 + 256 * RS + 16;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)win256_attn_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
+  vg_raise_lds_cap<win256_attn_kernel<D>>(lds);
   win256_attn_kernel<D><<<dim3(p.H, p.Bw), 256, lds, st>>>(p);
   VG_LAUNCH_CHECK();
   return VG_OK;

@@ -501,11 +501,7 @@ template <int DP, bool CAUSAL, int QB, int NW>
 int launch_dma(const AttnArgs& p, hipStream_t st) {
   constexpr int lds = 3 * 2 * 64 * 256;      // three stages of (K tile + V tile)
   constexpr int BQ = NW * 32 * QB;
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)attn_dma_kernel<DP, CAUSAL, QB, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    once = true;
-  }
+  vg_raise_lds_cap<attn_dma_kernel<DP, CAUSAL, QB, NW>>(lds);
   dim3 grid((p.Sq + BQ - 1) / BQ, p.Hq, p.B);
   attn_dma_kernel<DP, CAUSAL, QB, NW><<<grid, NW * 64, lds, st>>>(p);
   VG_LAUNCH_CHECK();
@@ -521,11 +517,7 @@ bool attn_dma_dv_eligible(const AttnArgs& p) {
 
 int attn_dma_dv_launch(const AttnArgs& p, hipStream_t st) {
   constexpr int lds = 3 * (64 * 512 + 64 * 256);
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)attn_dma_d256v64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    once = true;
-  }
+  vg_raise_lds_cap<attn_dma_d256v64_kernel>(lds);
   dim3 grid(((p.Sq + 255) / 256) * p.nsplit, p.Hq, p.B);
   attn_dma_d256v64_kernel<<<grid, 512, lds, st>>>(p);
   VG_LAUNCH_CHECK();

@@ -15,7 +15,8 @@
 //                            W row once with 16-byte loads; HBM-bound by construction.  gemm_skinny_shortk_kernel: <= 4 rows against
 //                            short W rows (the mask product), a lane per output column.
 //   epi_rows_fast / epi_dispatch: the straight-line row-major side shared by every LDS-staged epilogue.
-// Routing: launch_gemm / route_* below (and vg_gemm_route for the bench).
+// Routing: gemm_plan in vg_gemm_route.h (host-only: the shape rules, the eligibility of every kernel, grid / gn / nt / LDS of the launch).  launch_gemm below
+// launches what the plan says; vg_gemm_route (bench.py, ops.linear, ops.linear_ln) answers from the same plan.
 #include "vg_gemm_common.h"
 
 constexpr int GBM = 128, GBN = 128;
@@ -927,160 +928,50 @@ static void launch_skinny(const GemmArgs& p, int batch, hipStream_t st) {
   else gemm_skinny_kernel<T, TO, 16, GLU><<<grid, 256, 0, st>>>(p);
 }
 
-// ---- routing of an M > 16 GEMM to a tile kernel (shared by the launcher and vg_gemm_route, which bench.py uses to
-// attribute launches to kernels).  Knobs are read once.
+// ---- routing of an M > 16 GEMM to a tile kernel: gemm_plan (vg_gemm_route.h) decides, launch_gemm launches what it says and vg_gemm_route (which
+// bench.py uses to attribute launches to kernels) answers from the same plan.  Knobs and the CU count are read once.
 static int env_knob(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
-static int knob_rr() { static const int v = env_knob("VG_GEMM_RR", 1); return v; }    // row-register kernel (K = 144 / 288): 0 off (A/B), 1 rule (M >= 65536 rows), 2 every eligible shape (tests)
-static int knob_p8() { static const int v = env_knob("VG_GEMM_P8", 1); return v; }    // 0: no 256-row tile routes (A/B), 2 / 3: the 256x256 / 256x192 kernel on every eligible bf16 shape
-// small problems with a short K: fewer than 256 tiles of 128x128 (the chip is not filled), K = 64 / 128 / 192 / 256 bf16 -> gemm_small64_kernel
-static bool route_small64(int64_t M, int64_t N, int64_t K, int es, int a_op, int wmode, int vec_out, int batch) {
-  if (es != 2 || a_op || wmode || !vec_out || M <= 16 || K % 64 != 0 || K > 256) return false;
-  return ((M + 127) / 128) * ((N + 127) / 128) * batch < 256;
-}
-// few K-steps per tile (K x element size <= 3 KB): the 64-byte-step kernel with four workgroups per CU
-// (measured r01, tools/bench_gemm.py: +20...50 % on the Hiera / tower shapes up to K = 1408, -10...15 % from K = 2304 up)
-static bool route_small_k(int64_t K, int es, int a_op) {
-  return K * es <= 3072 && a_op == 0;
-}
-// single-stage 128-byte-row kernel: the small-K shapes with at least four whole-line K steps (measured r01: +16...18 % on
-// Hiera stage 3 / 4 and +7...14 % on the tower shapes over the 64-byte-row kernel; K = 144 / 288 stay there)
-static bool route_s128(int64_t K, int es, int a_op) {
-  return route_small_k(K, es, a_op) && K * es >= 1024;
-}
-// 256x256 tile, 128x128 per wave: bf16, whole 128-byte K steps, and the 256-tiles must use the chip well: (useful
-// fraction of the tiles' area) x (fill of the rounds of 256 workgroups) >= 0.7 — Hiera's N = 576 outputs or 168-tile
-// grids stay on the 128x128 kernels (measured r01, tools/bench_gemm.py).  a_op == 1: a tile is 256 rows x 128 outputs
-static bool route_p8(int64_t M, int64_t N, int64_t K, int es, int a_op, int wmode, int vec_out, int batch, int* ntw_out, int* mtw_out) {
-  const int ntw = (int)(a_op == 1 ? (N + 127) / 128 : (N + 255) / 256), mtw = (int)((M + 255) / 256);
-  if (ntw_out) { *ntw_out = ntw; *mtw_out = mtw; }
-  const int w = knob_p8();
-  // (r02, persistent kernel + straight-line epilogue: from K x es = 2304 B — Hiera stage 4, InternVideo2 — the 256x256 kernel beats the
-  // single-stage 128x128 one by 2...9 %; K = 1024 / 576 stay there)
-  constexpr int smallk_min = 1152;     // r04: with the phase-split kernel also K = 576 (Hiera stage 3): C2 268.5 -> 266.7 ms same-box
-  if (!w || es != 2 || (route_small_k(K, es, a_op) && K * es < smallk_min) || wmode || K % (128 / es) != 0 || !vec_out) return false;
-  if (w == 2) return true;       // 2: force the 256x256 kernel on every eligible shape (4 = the shape rule, without the 256x192 tile)
-  const int64_t t256 = (int64_t)ntw * mtw * batch;
-  const double useful = (double)M * N / ((double)mtw * 256 * ntw * (a_op == 1 ? 128 : 256));
-  const double fill = (double)t256 / (double)(((t256 + 255) / 256) * 256);
-  return t256 >= 128 && useful * fill >= 0.7;
-}
-
-// 256 x 192 tiles (vg_gemm_p8n.hip, r05) instead of 256 x 256 when whole rounds x tile cost say so: cost = rounds of 256 workgroups x
-// (0.87 | 1) — measured r05 (tools/lab/p8n_ab.sh, same box): a narrow tile costs 0.83-0.90 of a wide one at equal rounds (it stages 7/8 of the
-// bytes for 3/4 of the MFMAs).  N = 576 is three exact 192-tiles against 2.25 of three 256-tiles (Hiera stage 3 fc2 195 -> 162 us, proj
-// 86 -> 55), Llama's q|k|v at M = 3361 two rounds of the narrow tile against two of the wide one (189 -> 170 us; r04's 128x128 route: 213).  Without a valid 256-route for the shape (under-filled or badly quantised grids) the narrow tile is judged by the
-// same fill rule.
-static bool route_p8n(int64_t M, int64_t N, int64_t K, int es, int a_op, int wmode, int vec_out, int batch, bool p8_ok, int* nt_out, int* mt_out) {
-  const int nt = (int)((N + 191) / 192), mt = (int)((M + 255) / 256);
-  if (nt_out) { *nt_out = nt; *mt_out = mt; }
-  if (es != 2 || a_op || wmode || K % 64 != 0 || K < 128 || !vec_out) return false;
-  if (knob_p8() == 3) return true;       // 3: force the 256x192 kernel on every eligible shape (tests: minimal K, tiny grids)
-  if (knob_p8() != 1 || (route_small_k(K, es, a_op) && K * es < 1152)) return false;      // (4: the shape rule without the narrow tile — A/B)
-  const int64_t t192 = (int64_t)nt * mt * batch, t256 = (int64_t)((N + 255) / 256) * mt * batch;
-  if (t192 < 128) return false;
-  const int64_t r192 = (t192 + 255) / 256, r256 = (t256 + 255) / 256;
-  if (!p8_ok) {
-    const double useful = (double)M * N / ((double)mt * 256 * nt * 192), fill = (double)t192 / (double)(r192 * 256);
-    return useful * fill >= 0.7;
-  }
-  return (double)r192 * 0.87 < 0.97 * (double)r256;
+static const GemmKnobs& gemm_knobs() { static const GemmKnobs k{env_knob("VG_GEMM_RR", 1), env_knob("VG_GEMM_P8", 1)}; return k; }
+static int gemm_ncu() {
+  static const int ncu = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+  return ncu;
 }
 
 template <typename T, typename TO>
 static int launch_gemm(const GemmArgs& p, int batch, hipStream_t st) {
-  if (p.M <= 16) {
+  const GemmPlan pl = gemm_plan(p, batch, (int)sizeof(T), sizeof(TO) == 2, gemm_knobs(), gemm_ncu());
+  if (pl.kernel == GEMM_SKINNY) {
     if (p.a_op == 1) launch_skinny<T, TO, true>(p, batch, st);
     else launch_skinny<T, TO, false>(p, batch, st);
-  } else {
-    // tile walk (gemm_tile_of): column groups of 4 N-tiles, i.e. a 4 x 16 patch of concurrent tiles per XCD
-    // (measured r01, tools/bench_gemm.py: 4 >= 8 > 16 > row-major on every C1 shape)
-    auto pick_gn = [&](int mt, int nt) { return nt < 4 ? nt : 4; };
-    GemmArgs q = p;
-    q.gn = pick_gn((p.M + GBM - 1) / GBM, (p.N + GBN - 1) / GBN);
-    // streaming stores for big outputs (>= 128 MB, r03) with sector-aligned rows (epi_store16)
-    q.nt = p.vec_out && (p.ldc * (int64_t)sizeof(TO)) % 64 == 0 && (int64_t)p.M * p.N * (int64_t)sizeof(TO) * batch >= (int64_t)128 << 20;
-    dim3 grid((p.N + GBN - 1) / GBN, (p.M + GBM - 1) / GBM, batch);
-    // the fp32 epilogue staging needs 4 x 64 x 68 floats = 69632 B of LDS whatever the K step
-    const int lds128 = 4 * 128 * 144;
-    static bool glds_attr = false;
-    if (!glds_attr) {
-      (void)hipFuncSetAttribute((const void*)gemm_tile_glds_kernel<T, TO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds128);
-      glds_attr = true;
-    }
-    const bool small_k = route_small_k(p.K, (int)sizeof(T), p.a_op);
-    int ntw, mtw;
-    // (r04: a padding-free power-of-two window GATHER rides on the phase-split kernel — Hiera stage 3's windowed qkv; everything else windowed
-    // stays on the 128x128 kernels)
-    const int wroute = ((knob_p8() == 1 || knob_p8() >= 3) && sizeof(T) == 2 && vg_gemm_p8_window_ok(p.wmode, p.wsh, p.wH, p.wW, p.wws)) ? 0 : p.wmode;
-    const bool big = route_p8(p.M, p.N, p.K, (int)sizeof(T), p.a_op, wroute, p.vec_out, batch, &ntw, &mtw) && vg_gemm_p8_eligible(p, batch);
-    int ntn, mtn;
-    const bool narrow = sizeof(T) == 2 && route_p8n(p.M, p.N, p.K, (int)sizeof(T), p.a_op, wroute, p.vec_out, batch, big, &ntn, &mtn) && vg_gemm_p8_eligible(p, batch);
-    if constexpr (sizeof(T) == 2) {
-      if (route_small64(p.M, p.N, p.K, 2, p.a_op, p.wmode, p.vec_out, batch) && !p.sa) {
-        const int nseg = p.K / 64;
-        const int lds = nseg * 2 * 64 * 128 > 4 * 32 * 36 * 4 ? nseg * 2 * 64 * 128 : 4 * 32 * 36 * 4;
-        dim3 grids((p.N + 63) / 64, (p.M + 63) / 64, batch);
-        static bool small_attr = false;
-        if (!small_attr) {
-          (void)hipFuncSetAttribute((const void*)gemm_small64_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-          small_attr = true;
-        }
-        gemm_small64_kernel<TO><<<grids, 256, lds, st>>>(q);
-        VG_LAUNCH_CHECK();
-        return VG_OK;
-      }
-    }
-    if constexpr (sizeof(T) == 2) {
-      // short K over very many rows (Hiera stages 1-2, the FPN laterals of those levels): A rows in registers, no tiles (vg_gemm_rr.hip)
-      if (knob_rr() && vg_gemm_rr_eligible(p, batch, sizeof(TO) == 2) && (knob_rr() == 2 || p.M >= 65536)) {
-        static const int ncu_rr = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-        return vg_gemm_rr_launch(q, ncu_rr, st);
-      }
-    }
-    if (narrow) {
+    VG_LAUNCH_CHECK();
+    return VG_OK;
+  }
+  vg_raise_lds_cap<gemm_tile_glds_kernel<T, TO, true>>(GEMM_GLDS_LDS);      // on every tile launch, whichever kernel takes it
+  GemmArgs q = p;
+  q.gn = pl.gn; q.nt = pl.nt;
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  switch (pl.kernel) {
+    case GEMM_SKINNY: break;
+    case GEMM_SMALL64:
       if constexpr (sizeof(T) == 2) {
-        q.gn = pick_gn(mtn, ntn);
-        q.nbatch = batch;
-        static const int ncu = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-        const int64_t tot = (int64_t)ntn * mtn * batch;
-        return vg_gemm_p8n_launch(q, sizeof(TO) == 2, (int)(tot > ncu ? ncu : tot), st);
+        vg_raise_lds_cap<gemm_small64_kernel<TO>>(64 * 1024);      // K = 256 takes exactly the default cap
+        gemm_small64_kernel<TO><<<grid, 256, pl.lds, st>>>(q);
       }
-    }
-    if (big) {
-      if constexpr (sizeof(T) == 2) {
-        q.gn = pick_gn(mtw, ntw);
-        q.nbatch = batch;
-        // persistent: one workgroup per CU walks the tile queue
-        static const int ncu = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-        const int64_t tot = (int64_t)ntw * mtw * batch;
-        return vg_gemm_p8_launch(q, sizeof(TO) == 2, (int)(tot > ncu ? ncu : tot), st);
-      }
-    } else if (route_s128(p.K, (int)sizeof(T), p.a_op)) {
-      gemm_tile_s128_kernel<T, TO><<<grid, 256, 4 * 32 * 68 * 4, st>>>(q);
-    } else if (small_k) {
-      gemm_tile_k64b_kernel<T, TO><<<grid, 256, 4 * 32 * 68 * 4, st>>>(q);
-    } else if (p.a_op == 1) {       // SwiGLU in the epilogue: a tile = 128 rows x 64 outputs (gate | up halves)
-      dim3 gridg((p.N + 63) / 64, (p.M + GBM - 1) / GBM, batch);
-      q.gn = pick_gn((p.M + GBM - 1) / GBM, (p.N + 63) / 64);
-      gemm_tile_glds_kernel<T, TO, true><<<gridg, 256, lds128, st>>>(q);
-    } else if (p.wmode) {
-      gemm_tile_glds_kernel<T, TO, true><<<grid, 256, lds128, st>>>(q);
-    } else gemm_tile_glds_kernel<T, TO, true><<<grid, 256, lds128, st>>>(q);
+      break;
+    case GEMM_RR: return vg_gemm_rr_launch(q, gemm_ncu(), st);
+    case GEMM_P8N: q.nbatch = batch; return vg_gemm_p8n_launch(q, sizeof(TO) == 2, pl.gx, st);
+    case GEMM_P8: q.nbatch = batch; return vg_gemm_p8_launch(q, sizeof(TO) == 2, pl.gx, st);
+    case GEMM_S128: gemm_tile_s128_kernel<T, TO><<<grid, 256, pl.lds, st>>>(q); break;
+    case GEMM_K64B: gemm_tile_k64b_kernel<T, TO><<<grid, 256, pl.lds, st>>>(q); break;
+    case GEMM_GLDS:
+    case GEMM_GLDS_GLU: gemm_tile_glds_kernel<T, TO, true><<<grid, 256, pl.lds, st>>>(q); break;
   }
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
-
-
-// vg_gemm_window passes its geometry to the shared body through this thread-local (the body is vg_gemm's)
-struct GemmWindow { int mode, H, W, ws; const void* zrow; };
-static thread_local GemmWindow g_window{0, 0, 0, 0, nullptr};
-// vg_gemm_ln: the LayerNorm of the A rows rides the same way
-struct GemmLn { const float* w; const float* b; float eps; bool on; };
-static thread_local GemmLn g_ln{nullptr, nullptr, 0.f, false};
 
 // ---- split-K for grids that leave most of the chip idle (few 128x128 tiles, long K): K slices on blockIdx.z, fp32 partials,
 // one pass that sums them and applies the usual epilogue
@@ -1108,18 +999,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* part, i
 
 template <typename T, typename TO>
 static int launch_gemm_splitk(GemmArgs p, hipStream_t st) {
-  static bool attr = false;
-  const int lds128 = 4 * 128 * 144;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tile_glds_kernel<T, TO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds128);
-    attr = true;
-  }
+  const int lds128 = GEMM_GLDS_LDS;
+  vg_raise_lds_cap<gemm_tile_glds_kernel<T, TO, true>>(lds128);
   constexpr int BK = 128 / (int)sizeof(T);
   const int nk = (p.K + BK - 1) / BK;
   p.kchunk = ((nk + p.ksplit - 1) / p.ksplit) * BK;
   p.ksplit = (p.K + p.kchunk - 1) / p.kchunk;         // no empty slices
   const int nt = (p.N + GBN - 1) / GBN, mt = (p.M + GBM - 1) / GBM;
-  p.gn = nt < 4 ? nt : 4;
+  p.gn = gemm_gn(nt);
   if (p.ksplit > 1) {
     gemm_tile_glds_kernel<T, TO, true><<<dim3(nt, mt, p.ksplit), 256, lds128, st>>>(p);
     const int64_t groups = (int64_t)p.M * (p.N / 8);
@@ -1194,15 +1081,11 @@ extern "C" int vg_quantize_fp8_rows(const void* x, int64_t ldx, uint8_t* q, int6
 
 template <typename TO>
 static int launch_gemm_f8(const GemmArgs& p, hipStream_t st) {
-  static bool attr = false;
-  const int lds128 = 4 * 128 * 144;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tile_glds_kernel<uint8_t, TO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds128);
-    attr = true;
-  }
+  const int lds128 = GEMM_GLDS_LDS;
+  vg_raise_lds_cap<gemm_tile_glds_kernel<uint8_t, TO, true>>(lds128);
   GemmArgs q = p;
   const int nt = p.a_op == 1 ? (p.N + 63) / 64 : (p.N + GBN - 1) / GBN, mt = (p.M + GBM - 1) / GBM;
-  q.gn = nt < 4 ? nt : 4;
+  q.gn = gemm_gn(nt);
   gemm_tile_glds_kernel<uint8_t, TO, true><<<dim3(nt, mt, 1), 256, lds128, st>>>(q);
   VG_LAUNCH_CHECK();
   return VG_OK;
@@ -1230,24 +1113,37 @@ extern "C" int vg_gemm_f8(const uint8_t* A8, int64_t lda, const float* a_scale, 
   return launch_gemm_f8<float>(p, (hipStream_t)stream);
 }
 
+// The plan of the contiguous, aligned, batch-1 call without an epilogue.  windowed: a window call whose geometry is not known here — no kernel's window
+// form is assumed (wsh = -1: the 256-row kernels do not take it)
 extern "C" int vg_gemm_route(int64_t M, int64_t N, int64_t K, int in_dtype, int a_op, int windowed) {
-  if (M <= 16) return 0;
-  const int es = in_dtype == VG_BF16 ? 2 : 4;
-  // 7: the row-register kernel (bf16 output, no LayerScale, activation none | GELU assumed — what the path runs at K = 144 / 288)
-  if (es == 2 && !a_op && knob_rr() && (K == 144 || K == 288) && N % 16 == 0 && (knob_rr() == 2 || M >= 65536)) return 7;
-  if (route_small64(M, N, K, es, a_op, windowed, 1, 1)) return 5;
-  const bool p8ok = route_p8(M, N, K, es, a_op, windowed, 1, 1, nullptr, nullptr);
-  if (route_p8n(M, N, K, es, a_op, windowed, 1, 1, p8ok, nullptr, nullptr)) return 6;
-  if (p8ok) return 3;
-  if (route_s128(K, es, a_op)) return 4;
-  if (route_small_k(K, es, a_op)) return 2;
-  return 1;
+  auto i32 = [](int64_t v) { return (int)(v < 0x7fffffff ? v : 0x7fffffff); };
+  GemmArgs p{};
+  p.M = i32(M); p.N = i32(N); p.K = i32(K);
+  p.lda = p.ldw = K; p.ldc = N;
+  p.vec_out = 1; p.a_op = a_op; p.gn = 1; p.wmode = windowed ? 1 : 0; p.wsh = -1;
+  static const int code[] = {0 /* skinny */, 5 /* small64 */, 7 /* rr */, 6 /* p8n */, 3 /* p8 */, 4 /* s128 */, 2 /* k64b */, 1 /* glds */, 1 /* glds, SwiGLU tiles */};
+  return code[gemm_plan(p, 1, in_dtype == VG_BF16 ? 2 : 4, in_dtype == VG_BF16, gemm_knobs(), 256).kernel];
 }
 
-extern "C" int vg_gemm(const void* A, int64_t lda, int64_t sA, const void* W, int64_t ldw, int64_t sW,
-                       void* C, int64_t ldc, int64_t sC, const float* bias, const float* gamma,
-                       const void* R, int64_t ldr, int64_t sR, int M, int N, int K, int batch,
-                       int in_dtype, int out_dtype, int act, int a_op, vg_stream_t stream) {
+// What vg_gemm_window and vg_gemm_ln add to a vg_gemm call
+struct GemmWindow { int mode, H, W, ws; const void* zrow; };      // mode 0: none
+struct GemmLn { const float* w; const float* b; float eps; };
+
+// vg_gemm_window's own checks (vg_gemm_ln's window form makes them too); M: the rows of the window-order matrix
+static int gemm_window_rows(int mode, int B, int H, int Wd, int ws, const void* zero_row, int64_t* M) {
+  VG_CHECK((mode == 1 || mode == 2) && B > 0 && H > 0 && Wd > 0 && ws > 0, VG_ERR_ARG, "vg_gemm_window: bad window mode=%d B=%d H=%d W=%d ws=%d", mode, B, H, Wd, ws);
+  VG_CHECK(mode != 1 || zero_row, VG_ERR_ARG, "vg_gemm_window: mode 1 needs a row of K zeros");
+  const int nH = (H + ws - 1) / ws, nW = (Wd + ws - 1) / ws;
+  *M = (int64_t)B * nH * nW * ws * ws;
+  VG_CHECK(*M > 16 && *M < (1ll << 31), VG_ERR_UNSUPPORTED, "vg_gemm_window: %lld rows", (long long)*M);
+  return VG_OK;
+}
+
+// The body of vg_gemm, vg_gemm_window (win.mode != 0) and vg_gemm_ln (ln != nullptr)
+static int gemm_body(const void* A, int64_t lda, int64_t sA, const void* W, int64_t ldw, int64_t sW,
+                     void* C, int64_t ldc, int64_t sC, const float* bias, const float* gamma,
+                     const void* R, int64_t ldr, int64_t sR, int M, int N, int K, int batch,
+                     int in_dtype, int out_dtype, int act, int a_op, vg_stream_t stream, const GemmWindow& win, const GemmLn* ln) {
   VG_CHECK(A && W && C, VG_ERR_ARG, "vg_gemm: null pointer");
   VG_CHECK(M >= 0 && N > 0 && K > 0 && batch >= 1, VG_ERR_ARG, "vg_gemm: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);
   if (M == 0) return VG_OK;
@@ -1263,21 +1159,16 @@ extern "C" int vg_gemm(const void* A, int64_t lda, int64_t sA, const void* W, in
   VG_CHECK(a_op == 0 || M <= 16 || (vec_out && !R && !gamma && batch == 1 && act == VG_ACT_NONE), VG_ERR_UNSUPPORTED,
            "vg_gemm: a_op=1 with M > 16 needs 16-byte aligned C rows and no residual / LayerScale / activation / batch");
   GemmArgs p{A, W, C, bias, gamma, R, lda, ldw, ldc, ldr, sA, sW, sC, sR, M, N, K, act, vec_out, a_op, 1, 0, 0, 0, 0, 0, 0, -1, nullptr};
-  if (g_window.mode) {
-    VG_CHECK(g_window.mode != 2 || vec_out, VG_ERR_UNSUPPORTED, "vg_gemm_window: scattered C/R rows must be 16-byte aligned (ldc=%lld ldr=%lld)",
+  if (win.mode) {
+    VG_CHECK(win.mode != 2 || vec_out, VG_ERR_UNSUPPORTED, "vg_gemm_window: scattered C/R rows must be 16-byte aligned (ldc=%lld ldr=%lld)",
              (long long)ldc, (long long)ldr);
-    p.wmode = g_window.mode; p.wH = g_window.H; p.wW = g_window.W; p.wws = g_window.ws;
-    p.wnH = (g_window.H + g_window.ws - 1) / g_window.ws; p.wnW = (g_window.W + g_window.ws - 1) / g_window.ws;
-    p.zrow = g_window.zrow;
-    auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-    const int a = lg2(p.wws), b = lg2(p.wnW), c = lg2(p.wnH);
-    p.wsh = (a >= 0 && b >= 0 && c >= 0) ? (a | (b << 8) | (c << 16)) : -1;
+    gemm_set_window(p, win.mode, win.H, win.W, win.ws, win.zrow);
   }
   hipStream_t st = (hipStream_t)stream;
-  if (g_ln.on) {
-    p.ln_w = g_ln.w; p.ln_b = g_ln.b; p.ln_eps = g_ln.eps;
+  if (ln) {
+    p.ln_w = ln->w; p.ln_b = ln->b; p.ln_eps = ln->eps;
     // only the row-register kernel normalises its rows: anything else is the caller's vg_layernorm + vg_gemm
-    VG_CHECK(in_dtype == VG_BF16 && out_dtype == VG_BF16 && knob_rr() && vg_gemm_rr_eligible(p, batch, true) && (knob_rr() == 2 || M >= 65536),
+    VG_CHECK(in_dtype == VG_BF16 && out_dtype == VG_BF16 && gemm_plan(p, batch, 2, true, gemm_knobs(), 256).kernel == GEMM_RR,
              VG_ERR_UNSUPPORTED, "vg_gemm_ln: M=%d N=%d K=%d is not a row-register shape (bf16, K in {144, 288}, N %% 16 == 0, >= 65536 rows, no residual)", M, N, K);
   }
   if (in_dtype == VG_BF16 && out_dtype == VG_BF16) return launch_gemm<bf16_t, bf16_t>(p, batch, st);
@@ -1288,22 +1179,19 @@ extern "C" int vg_gemm(const void* A, int64_t lda, int64_t sA, const void* W, in
   return VG_ERR_UNSUPPORTED;
 }
 
-extern "C" int vg_gemm_ln(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias,
-                          const float* ln_w, const float* ln_b, float ln_eps, int64_t M, int N, int K, int act,
-                          int window, int B, int H, int Wd, int ws, const void* zero_row, int dtype, vg_stream_t stream);
+extern "C" int vg_gemm(const void* A, int64_t lda, int64_t sA, const void* W, int64_t ldw, int64_t sW,
+                       void* C, int64_t ldc, int64_t sC, const float* bias, const float* gamma,
+                       const void* R, int64_t ldr, int64_t sR, int M, int N, int K, int batch,
+                       int in_dtype, int out_dtype, int act, int a_op, vg_stream_t stream) {
+  return gemm_body(A, lda, sA, W, ldw, sW, C, ldc, sC, bias, gamma, R, ldr, sR, M, N, K, batch, in_dtype, out_dtype, act, a_op, stream, GemmWindow{}, nullptr);
+}
 
 extern "C" int vg_gemm_window(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias,
                               const float* gamma, const void* R, int64_t ldr, int N, int K, int in_dtype, int out_dtype, int act,
                               int mode, int B, int H, int Wd, int ws, const void* zero_row, vg_stream_t stream) {
-  VG_CHECK((mode == 1 || mode == 2) && B > 0 && H > 0 && Wd > 0 && ws > 0, VG_ERR_ARG, "vg_gemm_window: bad window mode=%d B=%d H=%d W=%d ws=%d", mode, B, H, Wd, ws);
-  VG_CHECK(mode != 1 || zero_row, VG_ERR_ARG, "vg_gemm_window: mode 1 needs a row of K zeros");
-  const int nH = (H + ws - 1) / ws, nW = (Wd + ws - 1) / ws;
-  const int64_t M = (int64_t)B * nH * nW * ws * ws;
-  VG_CHECK(M > 16 && M < (1ll << 31), VG_ERR_UNSUPPORTED, "vg_gemm_window: %lld rows", (long long)M);
-  g_window = GemmWindow{mode, H, Wd, ws, zero_row};
-  const int rc = vg_gemm(A, lda, 0, W, ldw, 0, C, ldc, 0, bias, gamma, R, ldr, 0, (int)M, N, K, 1, in_dtype, out_dtype, act, 0, stream);
-  g_window.mode = 0;
-  return rc;
+  int64_t M;
+  if (const int rc = gemm_window_rows(mode, B, H, Wd, ws, zero_row, &M)) return rc;
+  return gemm_body(A, lda, 0, W, ldw, 0, C, ldc, 0, bias, gamma, R, ldr, 0, (int)M, N, K, 1, in_dtype, out_dtype, act, 0, stream, GemmWindow{mode, H, Wd, ws, zero_row}, nullptr);
 }
 
 // y = act(LayerNorm_K(A) W^T + bias): the LayerNorm in front of Hiera's q|k|v and fc1 projections at the widths of stages 1 and 2 (hieradet.py:117-123,
@@ -1314,11 +1202,13 @@ extern "C" int vg_gemm_ln(const void* A, int64_t lda, const void* W, int64_t ldw
                           int window, int B, int H, int Wd, int ws, const void* zero_row, int dtype, vg_stream_t stream) {
   VG_CHECK(ln_w && ln_b, VG_ERR_ARG, "vg_gemm_ln: LayerNorm weight / bias missing");
   VG_CHECK(dtype == VG_BF16, VG_ERR_UNSUPPORTED, "vg_gemm_ln: bf16 only (dtype %d)", dtype);
-  g_ln = GemmLn{ln_w, ln_b, ln_eps, true};
-  int rc;
-  if (window) rc = vg_gemm_window(A, lda, W, ldw, C, ldc, bias, nullptr, nullptr, 0, N, K, dtype, dtype, act, 1, B, H, Wd, ws, zero_row, stream);
-  else if (M <= 0 || M >= (1ll << 31)) { vg_set_error("vg_gemm_ln: %lld rows", (long long)M); rc = VG_ERR_ARG; }
-  else rc = vg_gemm(A, lda, 0, W, ldw, 0, C, ldc, 0, bias, nullptr, nullptr, 0, 0, (int)M, N, K, 1, dtype, dtype, act, 0, stream);
-  g_ln.on = false;
-  return rc;
+  GemmWindow win{};
+  if (window) {
+    if (const int rc = gemm_window_rows(1, B, H, Wd, ws, zero_row, &M)) return rc;
+    win = GemmWindow{1, H, Wd, ws, zero_row};
+  } else {
+    VG_CHECK(M > 0 && M < (1ll << 31), VG_ERR_ARG, "vg_gemm_ln: %lld rows", (long long)M);
+  }
+  const GemmLn ln{ln_w, ln_b, ln_eps};
+  return gemm_body(A, lda, 0, W, ldw, 0, C, ldc, 0, bias, nullptr, nullptr, 0, 0, (int)M, N, K, 1, dtype, dtype, act, 0, stream, win, &ln);
 }

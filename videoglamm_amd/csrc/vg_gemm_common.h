@@ -1,32 +1,10 @@
-// Pieces shared by the GEMM translation units (vg_gemm.hip, vg_gemm_p8.hip): the launch record, the XCD-aware tile walk, the MFMA wrappers and
-// the straight-line row-major side of the LDS-staged epilogues.  See vg_gemm.hip's header for the kernel list.
+// Device pieces shared by the GEMM translation units (vg_gemm.hip, vg_gemm_p8.hip, vg_gemm_p8n.hip, vg_gemm_rr.hip, vg_gemm_rows.hip): the window row map, the
+// XCD-aware tile walk, the MFMA wrappers and the straight-line row-major side of the LDS-staged epilogues.  The launch record (GemmArgs) and every routing
+// rule live in vg_gemm_route.h, which is host-only.  See vg_gemm.hip's header for the kernel list.
 #pragma once
 #include "vg_common.h"
+#include "vg_gemm_route.h"
 #include <stdlib.h>
-
-struct GemmArgs {
-  const void* A; const void* W; void* C; const float* bias; const float* gamma; const void* R;
-  int64_t lda, ldw, ldc, ldr, sA, sW, sC, sR;
-  int M, N, K, act;
-  int vec_out;  // C/R rows are 16-byte aligned: the epilogue stores whole 16-byte chunks
-  int a_op;     // 1: W holds gate|up rows ([2N,K]); output column n = silu(A.gate_n)*(A.up_n) (skinny path only)
-  int gn;       // tile order: column groups of gn N-tiles, M-tiles fastest-but-one inside a group (see gemm_tile_of)
-  // window-order <-> image-order row maps (vg_gemm_window): wmode 1 = A rows are gathered from an image-order tensor
-  // (window_partition fused into the load), 2 = C and R rows are scattered to / read from image order (window_unpartition
-  // + residual add fused into the epilogue).  GEMM row m is always the window-order index.
-  int wmode, wH, wW, wws, wnH, wnW;
-  int wsh;      // >= 0: ws, wnW, wnH are powers of two, their log2 packed as ws | nW << 8 | nH << 16 (gemm_window_row's shift path); -1: divide
-  const void* zrow;   // K zeros: source of the padded window rows (the LDS-DMA cannot zero-fill)
-  // fp8 operands (vg_gemm_f8): C = (A8 . W8^T) * sa[m] * sw[n] — one fp32 scale per A row (token) and per W row (output)
-  const float* sa; const float* sw;
-  // split-K (vg_gemm_splitk, 128x128 LDS-DMA kernel only): blockIdx.z = K slice of kchunk elements; raw fp32 partial tiles
-  // go to part[z][M][N], a second kernel sums them and applies the epilogue
-  int ksplit, kchunk; float* part;
-  int nbatch;   // persistent 256x256 kernel: batch count (tiles of all batch entries form one queue)
-  int nt;       // output tiles leave with non-temporal (streaming) stores: large outputs whose rows are whole 64-byte sectors (launch_gemm)
-  // LayerNorm over K in front of the contraction (vg_gemm_ln; the row-register kernel only): A rows are normalised as they arrive in registers
-  const float* ln_w; const float* ln_b; float ln_eps;
-};
 
 // window-order row m -> image-order row, or -1 for a padding row (backbones/utils.py:16-38 window_partition).
 // r03: when the window side and the window counts are powers of two (every Hiera stage of a 1024^2 input: 8 / 4 / 16 / 8-token windows on
@@ -93,7 +71,7 @@ __device__ __forceinline__ void epi_store16(void* ptr, const u32x4_t& v, int nt 
   // Hiera's stage-2 GEMMs, whose outputs (150-600 MB) are read by the next kernel long after they have left the caches: the 128x128
   // kernels are bound by their output stores (a build without them: -35...50 %), and with nt stores qkv runs 389 -> 252 us, fc1 487 -> 338,
   // proj 132 -> 112; stage 1's fc1 773 -> 646.  Rows that are not whole 64-byte sectors (N = 432, 144: partial sectors want the cache to
-  // merge them) lose 3-7 %, hence the rule in launch_gemm.  Inline asm: hipcc merges "if (nt) __builtin_nontemporal_store(...) else
+  // merge them) lose 3-7 %, hence the rule in gemm_plan (vg_gemm_route.h).  Inline asm: hipcc merges "if (nt) __builtin_nontemporal_store(...) else
   // plain store" into one plain store — the hint is dropped.
   if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(ptr), "v"(v) : "memory");
   else *(u32x4_t*)ptr = v;
@@ -198,12 +176,7 @@ __device__ __forceinline__ bool epi_dispatch(int act, bool res, bool gam, F&& f)
 #undef VG_EPI_CASE
 }
 
-// vg_gemm_p8.hip: the phase-split 256x256-tile bf16 kernel (launched from launch_gemm's 256x256 route)
-bool vg_gemm_p8_eligible(const GemmArgs& p, int batch);
-bool vg_gemm_p8_window_ok(int wmode, int wsh, int wH, int wW, int wws);
-int vg_gemm_p8_launch(const GemmArgs& q, int out_is_bf16, int wgs, hipStream_t st);
-// vg_gemm_p8n.hip: the same pipeline on 256 x 192 tiles (launch_gemm's route_p8n decides)
-int vg_gemm_p8n_launch(const GemmArgs& q, int out_is_bf16, int wgs, hipStream_t st);
-// vg_gemm_rr.hip: the row-register kernel for K = 144 / 288 over very many rows (A rows in registers, W chunks in LDS; launch_gemm's short-K route)
-bool vg_gemm_rr_eligible(const GemmArgs& p, int batch, bool out_is_bf16);
-int vg_gemm_rr_launch(const GemmArgs& q, int ncu, hipStream_t st);
+// the launchers of the other translation units; gemm_plan (vg_gemm_route.h) decides who runs and with how many workgroups
+int vg_gemm_p8_launch(const GemmArgs& q, int out_is_bf16, int wgs, hipStream_t st);      // vg_gemm_p8.hip: the phase-split 256x256-tile bf16 kernel
+int vg_gemm_p8n_launch(const GemmArgs& q, int out_is_bf16, int wgs, hipStream_t st);     // vg_gemm_p8n.hip: the same pipeline on 256 x 192 tiles
+int vg_gemm_rr_launch(const GemmArgs& q, int ncu, hipStream_t st);                       // vg_gemm_rr.hip: the row-register kernel for K = 144 / 288 over very many rows

@@ -469,27 +469,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tile_p8_kernel(GemmArgs p) {
 
 }  // namespace
 
-// the window forms this kernel takes: A rows gathered (mode 1) or C / R rows scattered (mode 2), windows a power of two that tile the image exactly (no padding rows: the 32-bit
-// source offsets cannot reach the zero row)
-bool vg_gemm_p8_window_ok(int wmode, int wsh, int wH, int wW, int wws) {
-  return (wmode == 1 || wmode == 2) && wsh >= 0 && wws > 0 && wH % wws == 0 && wW % wws == 0;
-}
-
-// Launcher (vg_gemm.hip's route_w128 decides; this only checks what the 32-bit source offsets need)
-bool vg_gemm_p8_eligible(const GemmArgs& p, int batch) {
-  const int64_t arows = p.M, wrows = p.a_op == 1 ? 2 * (int64_t)p.N : p.N;
-  const bool win_ok = p.wmode == 0 || (vg_gemm_p8_window_ok(p.wmode, p.wsh, p.wH, p.wW, p.wws) && !(p.wmode == 2 && p.a_op == 1));
-  return p.K % 64 == 0 && p.K >= 128 && arows * p.lda * 2 < (int64_t)1 << 32 && wrows * p.ldw * 2 < (int64_t)1 << 32 && !p.sa && win_ok && p.vec_out;
-}
-
+// Launcher (gemm_plan in vg_gemm_route.h decides, window forms and 32-bit source offsets included)
 template <typename TO>
 static int p8_launch(const GemmArgs& q, int wgs, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tile_p8_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  gemm_tile_p8_kernel<TO><<<wgs, 512, 160 * 1024, st>>>(q);
+  vg_raise_lds_cap<gemm_tile_p8_kernel<TO>>(GEMM_P8_LDS);
+  gemm_tile_p8_kernel<TO><<<wgs, 512, GEMM_P8_LDS, st>>>(q);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }

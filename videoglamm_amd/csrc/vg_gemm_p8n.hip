@@ -4,7 +4,7 @@
 // 144 + 132 launches per 32-frame clip) fills 2.25 of its 3 column tiles — a quarter of the MFMAs multiply padding —, Llama's q|k|v at
 // M = 3361 is 312 tiles = 1.22 rounds (the second round runs 56 workgroups), CLIP's fc2 148 tiles = 0.58 of a round; the vendor library was
 // 1.3-1.6x ahead on exactly these shapes (tools/gemm_vs_lib.py, r04).  With 192 columns N = 576 is three exact tiles, q|k|v 416 tiles of 0.75
-// the work, CLIP's fc2 222 tiles in one round: launch_gemm's cost model (rounds x tile width) picks the shape per problem.
+// the work, CLIP's fc2 222 tiles in one round: route_p8n's cost model (vg_gemm_route.h: rounds x tile width) picks the shape per problem.
 //
 // Same pipeline as the 256 x 256 kernel — four phases per 64-element K step, two wave groups one barrier apart, half-tiles double-buffered
 // with counted vmcnt waits, LDS-DMA through inline asm, the next tile's first loads issued in front of the epilogue, wave-private slab
@@ -384,19 +384,15 @@ __global__ __launch_bounds__(512, 2) void gemm_tile_p8n_kernel(GemmArgs p) {
 
 template <typename TO>
 int p8n_launch(const GemmArgs& q, int wgs, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tile_p8n_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-    attr = true;
-  }
-  gemm_tile_p8n_kernel<TO><<<wgs, 512, 144 * 1024, st>>>(q);
+  vg_raise_lds_cap<gemm_tile_p8n_kernel<TO>>(GEMM_P8N_LDS);
+  gemm_tile_p8n_kernel<TO><<<wgs, 512, GEMM_P8N_LDS, st>>>(q);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }
 
 }  // namespace
 
-// (eligibility = vg_gemm_p8_eligible's without the SwiGLU form: launch_gemm checks it)
+// (eligibility = the 256x256 kernel's without the SwiGLU form: gemm_plan in vg_gemm_route.h checks it)
 int vg_gemm_p8n_launch(const GemmArgs& q, int out_is_bf16, int wgs, hipStream_t st) {
   return out_is_bf16 ? p8n_launch<bf16_t>(q, wgs, st) : p8n_launch<float>(q, wgs, st);
 }

@@ -238,11 +238,7 @@ template <int PRO, bool ROPE>
 int launch_rows(const RowsArgs& a, hipStream_t st) {
   const int nseg = a.g.K / 64;
   const int lds = nseg * 2 * 64 * 128 + 4 * 32 * 36 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_rows64_kernel<PRO, ROPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    attr = true;
-  }
+  vg_raise_lds_cap<gemm_rows64_kernel<PRO, ROPE>>(96 * 1024);
   // column tiles per workgroup: as many as keep every resident workgroup slot (1 per CU at K = 256, 4 at K = 64) busy — the A tile (and its LayerNorm) is then staged once per
   // `ntile` outputs tiles instead of once per tile (measured r05, norm3 -> linear1 -> ReLU at M = 4096, N = 2048: 33.8 us with one tile each)
   const int mt = (a.g.M + 63) / 64, nt = a.g.N / 64;

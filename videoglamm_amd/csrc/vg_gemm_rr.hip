@@ -298,14 +298,10 @@ __global__ __launch_bounds__(512, 1) void gemm_rr_kernel(GemmArgs p) {
 
 template <int KS, bool RESIDENT>
 static int rr_launch_v(const GemmArgs& q, int wgs, size_t lds, hipStream_t st) {
-#define VG_RR_GO(A, R, L)                                                                                                                       \
-  do {                                                                                                                                          \
-    static bool attr = false;                                                                                                                   \
-    if (!attr) {                                                                                                                                \
-      (void)hipFuncSetAttribute((const void*)gemm_rr_kernel<KS, RESIDENT, A, R, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-      attr = true;                                                                                                                              \
-    }                                                                                                                                           \
-    gemm_rr_kernel<KS, RESIDENT, A, R, L><<<wgs, 512, lds, st>>>(q);                                                                            \
+#define VG_RR_GO(A, R, L)                                                        \
+  do {                                                                           \
+    vg_raise_lds_cap<gemm_rr_kernel<KS, RESIDENT, A, R, L>>(GEMM_RR_LDS_CAP);    \
+    gemm_rr_kernel<KS, RESIDENT, A, R, L><<<wgs, 512, lds, st>>>(q);             \
   } while (0)
   const bool ln = q.ln_w || q.ln_b;
   if (ln) {
@@ -321,20 +317,9 @@ static int rr_launch_v(const GemmArgs& q, int wgs, size_t lds, hipStream_t st) {
 
 }  // namespace
 
-// K in {144, 288}, bf16 in and out, N a multiple of 16, 16-byte aligned C / R rows, act none | GELU (GELU without a residual), no LayerScale / fp8 scales / batch
-bool vg_gemm_rr_eligible(const GemmArgs& p, int batch, bool out_is_bf16) {
-  return (p.K == 144 || p.K == 288) && out_is_bf16 && batch == 1 && !p.a_op && !p.sa && !p.gamma && p.vec_out && p.N % 16 == 0 && p.N >= 16 &&
-         (p.act == VG_ACT_NONE || (p.act == VG_ACT_GELU && !p.R)) && p.ksplit <= 1 && !((p.ln_w || p.ln_b) && p.R) &&
-         // the streamed form's LDS: bias per 64-column chunk + gamma | beta + the epilogue slabs + two weight slots (vg_gemm_rr_launch) within 158 KB
-         (size_t)((p.N + 63) / 64) * 256 + 8 * (size_t)p.K + 8 * 4096 + 2 * 64 * (size_t)(p.K * 2 + 16) <= 158 * 1024;
-}
-
+// (what this kernel requires of a call, and the form — workgroups, LDS, resident or streamed weight chunks — are in vg_gemm_route.h)
 int vg_gemm_rr_launch(const GemmArgs& q, int ncu, hipStream_t st) {
-  const int npanel = (q.M + 255) / 256, wgs = npanel < ncu ? npanel : ncu, nch = (q.N + 63) / 64;
-  const size_t slot = 64 * (size_t)(q.K * 2 + 16), fixed = (size_t)nch * 256 + ((q.ln_w || q.ln_b) ? 8 * (size_t)q.K : 0) + 8 * 4096;   // bias | gamma, beta | slabs
-  if (q.K == 144) {
-    if (fixed + nch * slot <= 158 * 1024) return rr_launch_v<9, true>(q, wgs, fixed + nch * slot, st);
-    return rr_launch_v<9, false>(q, wgs, fixed + 2 * slot, st);
-  }
-  return rr_launch_v<18, false>(q, wgs, fixed + 2 * slot, st);
+  const GemmRrForm f = gemm_rr_form(q, ncu);
+  if (q.K == 144) return f.resident ? rr_launch_v<9, true>(q, f.wgs, f.lds, st) : rr_launch_v<9, false>(q, f.wgs, f.lds, st);
+  return rr_launch_v<18, false>(q, f.wgs, f.lds, st);
 }

@@ -233,12 +233,8 @@ extern "C" int vg_gemm_w4a8_supported(int64_t N, int64_t K) { return w4a8_spl_sh
 
 template <typename TO>
 static int launch_w4a8(const W4A8Args& p, hipStream_t st) {
-  static bool attr = false;
   const int lds = 4 * 64 * 68 * 4;      // the epilogue's staging (68 KB) covers the two 24 KB stages
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_w4a8_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
+  vg_raise_lds_cap<gemm_w4a8_kernel<TO>>(lds);
   W4A8Args q = p;
   const int nt = p.a_op == 1 ? (p.N + 63) / 64 : (p.N + 127) / 128, mt = (p.M + 127) / 128;
   q.gn = nt < 4 ? nt : 4;

@@ -260,11 +260,7 @@ int launch_mlp(const MlpArgs& a, hipStream_t st) {
   constexpr int RSX = C * 2 + 16;
   constexpr int lds_x = 128 * RSX, lds_w = 32 * RSX + C * 72, lds_e = 4 * 4096;
   constexpr int lds = lds_x > lds_w ? (lds_x > lds_e ? lds_x : lds_e) : (lds_w > lds_e ? lds_w : lds_e);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)mlp_rows_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
+  vg_raise_lds_cap<mlp_rows_kernel<C>>(lds);
   mlp_rows_kernel<C><<<dim3((a.M + 127) / 128), 256, lds, st>>>(a);
   VG_LAUNCH_CHECK();
   return VG_OK;

@@ -423,12 +423,11 @@ extern "C" int vg_twoway_image_update(const void* xpe, const void* x, const void
   const int lds = (TP == 8 ? NC * 512 : 0) + 256 * NC * 2 + NC * 4 + NW * 16384;
   const int rows_wg = 32 * NW * a.iters;
   dim3 grid((P + rows_wg - 1) / rows_wg, N);
-  static bool attr8 = false, attr16 = false;
   if (TP == 8) {
-    if (!attr8) { (void)hipFuncSetAttribute((const void*)twoway_image_update_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr8 = true; }
+    vg_raise_lds_cap<twoway_image_update_kernel<8>>(lds);
     twoway_image_update_kernel<8><<<grid, NW * 64, lds, stream>>>(a);
   } else {
-    if (!attr16) { (void)hipFuncSetAttribute((const void*)twoway_image_update_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr16 = true; }
+    vg_raise_lds_cap<twoway_image_update_kernel<16>>(lds);
     twoway_image_update_kernel<16><<<grid, NW * 64, lds, stream>>>(a);
   }
   VG_LAUNCH_CHECK();
@@ -446,8 +445,7 @@ extern "C" int vg_mask_upscale(const void* x, const void* w0, const float* b0, c
   UpscaleArgs a{(const bf16_t*)x, (const bf16_t*)w0, b0, (const bf16_t*)s1, ln_w, ln_b, (const bf16_t*)w1, b1, (const bf16_t*)s0, (const bf16_t*)hyper,
                 masks, eps, N, images, es, N >= 256 ? 8 : (N >= 64 ? 4 : 2)};
   const int lds = 256 * 512 + 128 * 128 + 32 * 64;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)mask_upscale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
+  vg_raise_lds_cap<mask_upscale_kernel>(lds);
   const int rows_wg = 128 * a.iters;
   dim3 grid((P + rows_wg - 1) / rows_wg, N);
   mask_upscale_kernel<<<grid, 256, lds, stream>>>(a);

@@ -314,7 +314,8 @@ def linear_ln(x, ln, w, bias=None, act=ACT_NONE, window=None):
                         1 if window is not None else 0, wa[0], wa[1], wa[2], wa[3],
                         _p(_zero_row(K, x.dtype, x.device)) if window is not None else None, BF16, _stream())
     if rc == -3:      # VG_ERR_UNSUPPORTED (include/vg_kernels.h)
-        # the launcher's own eligibility (alignment, output stride, LDS) is stricter than the route query: take the two-launch form
+        # the route query answers for the contiguous, aligned call (and, since it is built on the launcher's plan, knows the kernel's LDS bound); this
+        # call's own pointers and strides can still refuse (16-byte aligned output rows): take the two-launch form
         xn = layernorm(x, ln[0], ln[1], ln[2])
         return linear_window(xn, w, bias, *window, scatter=False, act=act) if window is not None else linear(xn, w, bias, act=act)
     _lib.check(rc, "vg_gemm_ln")

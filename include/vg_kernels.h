@@ -388,6 +388,27 @@ int vg_sample_partial_rows(const float* x, int64_t ldx, int n, int B, const void
                            int64_t* tok, int* fast_ws, vg_stream_t stream);
 int vg_sample_survivors(const float* x, int n, const void* params, int64_t* idx, float* prob, int cap, int* count, vg_stream_t stream);
 int vg_sample_philox(const uint64_t* seeds, const int* steps, int n, uint32_t* out, vg_stream_t stream);
+/* Per-token scores (csrc/vg_scores.hip): for the B rows x[b * ldx .. b * ldx + n) of fp32 logits (1 <= B <= 16, n >= 2,
+ *   ldx >= n in elements, finite inputs), ONE launch that reads no host value and can be captured into a graph.  Per row:
+ *   top1, top2 — the indices of the largest and the second-largest entry; ties go to the lower index, with a tied maximum top2 is the
+ *     second-lowest index that holds it (-0 counts as +0);
+ *   margin = x[top1] - x[top2], one fp32 subtraction: >= 0, exactly 0 on a tie;
+ *   logprob = log_softmax(x)[pick] on the raw logits (no temperature, no warpers).  The pick is the index in the packed key acc[b] that
+ *     vg_argmax_partial / vg_sample_partial* leave (read, not cleared), or tok[b]: exactly one of acc / tok is not NULL.  A pick outside
+ *     [0, n) gives logprob = NaN.
+ *   Slot j = step[b] (device int32: the counter the sampler reads, the index of the token being emitted; 0 = the prefill's token) receives
+ *   scores[b, j, 0..1] = (logprob, margin) (float32) and top2[b, j, 0..1] = (top1, top2) (int64); both arrays are [B, cap, 2].  j outside
+ *   [0, cap) writes nothing; no other element of either array is touched.
+ *   Determinism: row b of a B-row launch equals the one-row launch on that row bit for bit, and two launches on one input are bit-equal.  Up to
+ *   64 workgroups per row (slices of <= 2048 entries); a slice's softmax mass is vg_sample's fixed point, sum floor(expf(x - m) * 2^40) in
+ *   uint64 with m the slice's maximum (independent of the order of its terms); the row's last workgroup to arrive (self-resetting ticket)
+ *   rescales the slices' masses to the row's maximum in float64 and adds them in slice order.  The slicing is a function of n alone.
+ *   ws: B * vg_token_scores_workspace_ints() int32, zero-filled once, row b works in its own slice; may be NULL for n <= 2048 (one workgroup
+ *   per row).  VG_ERR_ARG without a launch: NULL x / scores / top2 / step, both or neither of acc / tok, n < 2, B outside 1..16, ldx < n,
+ *   cap <= 0, NULL ws with n > 2048. */
+int vg_token_scores_workspace_ints(void);
+int vg_token_scores_rows(const float* x, int64_t ldx, int n, int B, const uint64_t* acc, const int64_t* tok, const int* step, float* scores,
+                         int64_t* top2, int cap, int* ws, vg_stream_t stream);
 
 /* vg_decode_layer (r03): everything of a decoder layer behind the q|k|v projection as ONE launch — vg_decode_attention, then
  *   y_o = attn_out . Wo^T + resid (vg_decode_gemv), and when Wgu != NULL also act = SwiGLU(RMSNorm(y_o; norm_w, eps) . Wgu^T) and

@@ -97,6 +97,8 @@ def _sig(lib):
         "vg_sample_partial_rows": ([P, L, I, I, P, P, P, P, P, P, P], c_int),
         "vg_sample_survivors": ([P, I, P, P, P, I, P, P], c_int),
         "vg_sample_philox": ([P, P, I, P, P], c_int),
+        "vg_token_scores_workspace_ints": ([], c_int),
+        "vg_token_scores_rows": ([P, L, I, I, P, P, P, P, P, I, P, P], c_int),
         "vg_mlp3_grouped": ([P, L, L, P, P, P, P, P, P, P, L, L, I, I, I, I, I, I, ctypes.c_uint, P], c_int),
         "vg_decode_layer_roles": ([I, I, I, I, I, I], c_int),
         "vg_decode_layer_flag_ints": ([], c_int64),

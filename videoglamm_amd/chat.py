@@ -42,6 +42,8 @@ def get_args():
                                                               "next to caption.txt; the boxes are reduced on the device")
     p.add_argument("--save_rle", action="store_true", help="also write rle.json (frame -> object -> COCO RLE with a compressed counts string) "
                                                             "next to caption.txt; the masks are encoded on the device")
+    p.add_argument("--save_scores", action="store_true", help="also write scores.json (per generated token: id, log-probability, top-2 margin, "
+                                                               "the two largest logits' ids) next to caption.txt")
     return p.parse_args()
 
 
@@ -136,6 +138,17 @@ def write_rle(codes, save_dir):
         json.dump({str(t): {str(k): coco_encode_rle(c) for k, c in fr.items()} for t, fr in codes.items()}, fh)
 
 
+def write_scores(output_ids, scores, save_dir):
+    """scores.json: one entry per generated token, in order: its id, the log-probability the model gave it (raw logits; null where the kernel
+    wrote NaN), the margin between the two largest logits of its step, and their ids (inference(return_scores=True))"""
+    G = len(scores["logprob"])
+    ids = [int(t) for t in np.asarray(output_ids).reshape(-1)[-G:]] if G else []
+    rows = [{"id": ids[j], "logprob": None if np.isnan(scores["logprob"][j]) else float(scores["logprob"][j]), "margin": float(scores["margin"][j]),
+             "top1": int(scores["top2"][j][0]), "runner_up": int(scores["top2"][j][1])} for j in range(G)]
+    with open(os.path.join(save_dir, "scores.json"), "w") as fh:
+        json.dump(rows, fh)
+
+
 def main():
     args = get_args()
     if args.base_model_type.split("|")[0] != "vgpt":
@@ -162,7 +175,7 @@ def main():
             precision=args.precision)
         prompt = args.prompt_text or input("Please input your prompt: ")
         input_ids = conv_generator.apply_for_chat(prompt, type=kind, tokenizer=tokenizer)
-        extra = {k: True for k, on in (("return_boxes", args.save_boxes), ("return_rle", args.save_rle)) if on}
+        extra = {k: True for k, on in (("return_boxes", args.save_boxes), ("return_rle", args.save_rle), ("return_scores", args.save_scores)) if on}
         output_ids, video_segments, *video_extra = model.inference(images=enc_image, context_images=enc_context_image, images_for_sam=image_sam,
                                                                    input_ids=input_ids, resize_list=resize_list,
                                                                    original_size_list=original_size_list, max_new_tokens=args.max_new_tokens,
@@ -177,7 +190,9 @@ def main():
         if args.save_boxes:
             write_boxes(video_extra[0][0], save_dir)
         if args.save_rle:
-            write_rle(video_extra[-1][0], save_dir)
+            write_rle(video_extra[int(args.save_boxes)][0], save_dir)
+        if args.save_scores:
+            write_scores(output_ids.cpu().numpy(), video_extra[-1][0], save_dir)
         if args.prompt_text and args.video:
             break
 

@@ -12,7 +12,7 @@ import torch
 
 from . import ops
 from .prompts import BUCKETS, GROUP, batched_route, bucket, decode_rows, rows_cover, sampling_route
-from .vlm import IMAGE_TOKEN_INDEX, LlamaDecoder, RowsDecode, generate, splice, stage_mark
+from .vlm import IMAGE_TOKEN_INDEX, LlamaDecoder, RowsDecode, generate, splice, stage_mark, wants_scores
 
 BOUND_STEP = 256      # n_bound is rounded up to a multiple of this: groups of similar clips then reuse one RowsDecode and its captured graphs
 CLIP_FIELDS = ("images", "context_images", "images_for_sam", "input_ids", "resize_list", "original_size_list")
@@ -71,7 +71,7 @@ def generate_clips(params, cfg, towers, clips, max_new_tokens, eos_token_id=None
                    after_prefill=None, stages=None, before_clip=None):
     """vlm.generate() for B clips.  clips[b] = (images, context_images, input_ids): device frames and host int64 ids [L_b]; visuals[b], when
     given, replaces the towers for clip b (generate(visual=)).  samplings[b]: None (greedy) or clip b's dict(T, k, p, seed); traces[b]: optional
-    dict (trace["argmax"]).  before_clip(b) / after_prefill(b): called before clip b's towers / once its prefill and first token are enqueued.
+    dict (trace["argmax"]; trace["scores"] = True is replaced by the clip's per-token records as in generate()).  before_clip(b) / after_prefill(b): called before clip b's towers / once its prefill and first token are enqueued.
     stages: when a list, receives the marks "start" and "decode" (vlm.stage_mark) around the whole call.
     -> [(output ids host int64 [L_b + G_b], pred_embeddings device [N_b, 256])] per clip: exactly generate()'s result for that clip.
 
@@ -140,6 +140,9 @@ def _group(params, cfg, towers, clips, g0, g1, max_new_tokens, eos_token_id, tok
         dec._rows.clear()              # one batched state per decoder
         rows = dec._rows[key] = RowsDecode(dec, bucket(n), 0, n_bound)
     rows.route = routes[0]
+    scores = traces is not None and any(wants_scores(traces[b]) for b in range(g0, g1))
+    dec.set_scores(scores)
+    rows.set_scores(scores)
     seg_idx = cfg["seg_token_idx"]
     eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(e) for e in eos_token_id})
     ids_out, added = [], []

@@ -293,28 +293,36 @@ class VideoGLaMMForCausalLM:
 
     # ------------------------------------------------------------------ inference surface
     def inference(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
-                  max_new_tokens=32, use_sam2_video_branch=False, *, return_boxes=False, return_rle=False, return_masks=True, **sampling):
+                  max_new_tokens=32, use_sam2_video_branch=False, *, return_boxes=False, return_rle=False, return_masks=True, return_scores=False,
+                  **sampling):
         """R/model/VideoGLaMM.py:560-596.  Keyword-only extras: do_sample / temperature / top_k / top_p (override model.generation_config for
         this call), generator (the torch.Generator the sampling seed is drawn from) and return_boxes: a third return value
         [{frame: {obj: np.float32[4]}}] with the keys of the masks' dictionaries, the postproc.masks_to_boxes value (x_min, y_min, x_max, y_max;
         [1e8, 1e8, 0, 0] for an empty mask) of exactly the mask that is returned, reduced on the device before the masks are downloaded.
         return_rle: one more return value after that, [{frame: {obj: {"size": [H, W], "counts": [int, ...]}}}], COCO's uncompressed run-length code
         (postproc.mask_to_rle_pytorch's form) of the same masks, encoded on the device by one ops.mask_rle call for the whole clip.
-        return_masks=False (needs return_boxes or return_rle): the dense masks are not downloaded; the mask dictionaries keep their keys and hold None."""
+        return_masks=False (needs return_boxes or return_rle): the dense masks are not downloaded; the mask dictionaries keep their keys and hold None.
+        return_scores: one more return value, last: [{"logprob": float32 [G], "margin": float32 [G], "top2": int64 [G, 2]}] (host numpy, one
+        record per generated token): log_softmax of the raw fp32 logits at the token the model picked, the margin between the two largest logits
+        and their indices (vg_token_scores_rows inside the decode step).  One GPU only."""
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             torch.cuda.set_device(self.device)
         if use_sam2_video_branch:
             if self.config.use_sam2:
                 return self.inference_video_branch(images, context_images, images_for_sam, input_ids, resize_list,
                                                    original_size_list, max_new_tokens, return_boxes=return_boxes, return_rle=return_rle,
-                                                   return_masks=return_masks, **sampling)
+                                                   return_masks=return_masks, return_scores=return_scores, **sampling)
             raise ValueError("use_sam2_video_branch is True, but model is not configured to use SAM2")
         return self.inference_framewise(images, context_images, images_for_sam, input_ids, resize_list,
                                         original_size_list, max_new_tokens, return_boxes=return_boxes, return_rle=return_rle,
-                                        return_masks=return_masks, **sampling)
+                                        return_masks=return_masks, return_scores=return_scores, **sampling)
 
-    def _set_returns(self, return_boxes, return_rle=False, return_masks=True):
-        """this call's return_boxes / return_rle / return_masks; refusals come first, before any GPU work"""
+    def _set_returns(self, return_boxes, return_rle=False, return_masks=True, return_scores=False):
+        """this call's return_boxes / return_rle / return_masks / return_scores; refusals come first, before any GPU work"""
+        if return_scores and self.comm is not None:
+            raise NotImplementedError("return_scores runs on one GPU: the replicated decode of a multi-GPU model would produce the scores on "
+                                      "every rank; call the model on one GPU for them")
+        self._want_scores, self._scores = bool(return_scores), None
         if not return_masks and not (return_boxes or return_rle):
             raise ValueError("return_masks=False needs return_boxes=True or return_rle=True: the call would return nothing about the masks")
         if return_boxes and self.comm is not None:
@@ -328,7 +336,7 @@ class VideoGLaMMForCausalLM:
 
     def _returns(self):
         """the three keywords of this call, to hand on to a nested call"""
-        return dict(return_boxes=self._want_boxes, return_rle=self._want_rle, return_masks=self._want_masks)
+        return dict(return_boxes=self._want_boxes, return_rle=self._want_rle, return_masks=self._want_masks, return_scores=self._want_scores)
 
     def _resolve_sampling(self, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None):
         """this call's decoding mode; multi-GPU: every rank adopts rank 0's seed (the decode is replicated and must emit the same ids)"""
@@ -341,10 +349,16 @@ class VideoGLaMMForCausalLM:
         assert len(images) == 1 and input_ids.shape[0] == 1  # batch size is 1 (VideoGLaMM.py:252-253)
         # context_images=None: single-image prompt (CLIP -> image_mm_projector without pooling, arch.py:243-245,393-397)
         ctx = context_images[0] if context_images is not None else None
+        trace = self.capture
+        if self._want_scores:      # the records come back through generate()'s trace (a private one when nothing is being captured)
+            trace = {} if trace is None else trace
+            trace["scores"] = True
         out_ids, emb = generate(self.P, self._live_cfg(), self.towers, images[0].to(self.device), None if ctx is None else ctx.to(self.device),
                                 input_ids[0].cpu(), max_new_tokens, self._eos(),
                                 token_hook=self.token_hook, after_prefill=after_prefill, comm=self.comm,
-                                trace=self.capture, stages=self.stages, sampling=self._sampling)
+                                trace=trace, stages=self.stages, sampling=self._sampling)
+        if self._want_scores:
+            self._scores = trace["scores"]
         if self.capture is not None:
             self.capture["emb"] = emb
         return out_ids.unsqueeze(0), emb
@@ -436,6 +450,10 @@ class VideoGLaMMForCausalLM:
             codes = [flat[i * N:(i + 1) * N] for i in range(T)]
         return host, boxes, codes
 
+    def _with_scores(self, ret):
+        """an inference()'s return value, with [the scores] as its last element under return_scores"""
+        return ret + ([self._scores],) if self._want_scores else ret
+
     def _extras(self):
         """how many return values follow the masks: the boxes, then the codes"""
         return int(self._want_boxes) + int(self._want_rle)
@@ -487,15 +505,15 @@ class VideoGLaMMForCausalLM:
 
     def inference_framewise(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
                             max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None, empty_ok=False,
-                            return_boxes=False, return_rle=False, return_masks=True):
+                            return_boxes=False, return_rle=False, return_masks=True, return_scores=False):
         """R/model/VideoGLaMM.py:598-768 -> (output_ids [1,L+G], [ {frame: {obj: mask}} ]).  empty_ok: no [SEG] gives [{}] as the video branch
-        does, not the reference's exception (inference_prompts' meaning of such a prompt).  return_boxes / return_rle / return_masks: see inference()."""
-        self._set_returns(return_boxes, return_rle, return_masks)
+        does, not the reference's exception (inference_prompts' meaning of such a prompt).  return_boxes / return_rle / return_masks / return_scores: see inference()."""
+        self._set_returns(return_boxes, return_rle, return_masks, return_scores)
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens)
         if emb.shape[0] == 0 and empty_ok:
-            return (out_ids,) + self._result(None)
+            return self._with_scores((out_ids,) + self._result(None))
         if emb.shape[0] == 0:
             # the reference dereferences `.shape` of a tuple here (VideoGLaMM.py:732): same exception type
             raise AttributeError("'tuple' object has no attribute 'shape'")
@@ -514,13 +532,13 @@ class VideoGLaMMForCausalLM:
             if self.capture is not None:
                 self.capture["logits"] = logits
             res = self._download(self._binarize(logits))
-        return (out_ids,) + self._result(*res)
+        return self._with_scores((out_ids,) + self._result(*res))
 
     def inference_video_branch(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
                                max_new_tokens=32, *, do_sample=None, temperature=None, top_k=None, top_p=None, generator=None,
-                               return_boxes=False, return_rle=False, return_masks=True):
-        """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842).  return_boxes / return_rle / return_masks: see inference()."""
-        self._set_returns(return_boxes, return_rle, return_masks)
+                               return_boxes=False, return_rle=False, return_masks=True, return_scores=False):
+        """R/model/VideoGLaMM.py:770-879; empty dict when no [SEG] was emitted (:840-842).  return_boxes / return_rle / return_masks / return_scores: see inference()."""
+        self._set_returns(return_boxes, return_rle, return_masks, return_scores)
         self._resolve_sampling(do_sample, temperature, top_k, top_p, generator)
         sam = images_for_sam[0].to(self.device)
         # multi-GPU: frames shard for Hiera only (the propagation is a recurrence over frames) and every rank needs every frame's features:
@@ -530,7 +548,7 @@ class VideoGLaMMForCausalLM:
         graphed = self.comm is None and self.device.type == "cuda" and os.environ.get("VG_VIDEO_GRAPH", "1") == "1"
         out_ids, emb, feats = self._text_and_hiera(images, context_images, sam, input_ids, max_new_tokens, all_frames=streamed, static_feats=graphed)
         if emb.shape[0] == 0:
-            return (out_ids,) + self._result(None)
+            return self._with_scores((out_ids,) + self._result(None))
         hw = tuple(original_size_list[0])
         if self.comm is not None:
             # OBJECTS shard for the propagation
@@ -550,25 +568,26 @@ class VideoGLaMMForCausalLM:
             if fast:
                 res = self._download(out)
                 stage_mark(self.stages, "propagation")
-                return (out_ids,) + self._result(*res)
+                return self._with_scores((out_ids,) + self._result(*res))
             logits = out
         elif self._fast_masks():
             res = self._download(self.sam2.video_branch(sam, emb, hw, frame_feats=feats, as_masks=True))
             stage_mark(self.stages, "propagation")
-            return (out_ids,) + self._result(*res)
+            return self._with_scores((out_ids,) + self._result(*res))
         else:
             logits = self.sam2.video_branch(sam, emb, hw, frame_feats=feats)
         if self.capture is not None:
             self.capture["logits"] = logits
-        return (out_ids,) + self._result(*self._download(self._binarize(logits)))
+        return self._with_scores((out_ids,) + self._result(*self._download(self._binarize(logits))))
 
     # ------------------------------------------------------------------ several prompts about one clip
     def inference_prompts(self, images, context_images, images_for_sam, input_ids_list, resize_list, original_size_list,
                           max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                          generator=None, shared=None, return_boxes=False, return_rle=False, return_masks=True):
+                          generator=None, shared=None, return_boxes=False, return_rle=False, return_masks=True, return_scores=False):
         """B prompts ([1, L_b] or [L_b] each) about ONE clip -> (output ids [1, L_b + G_b] per prompt, {frame: {obj: mask}} per prompt).
         return_boxes adds a third list, {frame: {obj: np.float32[4]}} per prompt (see inference(); {} where the masks are {}); return_rle one more
-        after it, {frame: {obj: code}} per prompt; return_masks=False leaves None in the mask dictionaries (see inference()).
+        after it, {frame: {obj: code}} per prompt; return_masks=False leaves None in the mask dictionaries (see inference()); return_scores one more
+        list, last, the per-token records of every prompt (see inference()), in prompt order.
         Entry b means what inference(..., input_ids=input_ids_list[b]) means; a prompt without a [SEG] gets {} (as the video branch does,
         R/model/VideoGLaMM.py:840-842).  The towers, Hiera and the prefill of the shared prefix (system text + visual block, identical ids in
         every prompt) run once; SAM2 runs once with every prompt's [SEG] embeddings as its objects.  Sampling draws one seed per prompt from
@@ -580,7 +599,7 @@ class VideoGLaMMForCausalLM:
         from .prompts import GROUP, check_prompts
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_prompts() runs on one GPU: call inference() per prompt on a multi-GPU model")
-        self._set_returns(return_boxes, return_rle, return_masks)
+        self._set_returns(return_boxes, return_rle, return_masks, return_scores)
         ids_list = [torch.as_tensor(x).cpu().long() for x in input_ids_list]
         if not ids_list:
             raise NotImplementedError("inference_prompts() needs at least one prompt")
@@ -602,7 +621,7 @@ class VideoGLaMMForCausalLM:
                                        use_sam2_video_branch, dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                                                    generator=generator, **self._returns()))
         samplings = [resolve_sampling(self.generation_config, do_sample, temperature, top_k, top_p, generator) for _ in ids_list]
-        out_ids, segs, extras = [], [], [[] for _ in range(self._extras())]
+        out_ids, segs, extras = [], [], [[] for _ in range(self._extras() + int(self._want_scores))]
         for g in range(0, len(ids_list), GROUP):
             o, s, ex = self._prompts_group(images, context_images, images_for_sam, ids_list[g:g + GROUP], original_size_list, max_new_tokens,
                                            use_sam2_video_branch, samplings[g:g + GROUP])
@@ -615,7 +634,7 @@ class VideoGLaMMForCausalLM:
     def _prompts_alone(self, images, context_images, images_for_sam, ids_list, resize_list, original_size_list, max_new_tokens, video, sampling):
         """inference_prompts() as one inference() per prompt, in list order (each call draws its own sampling seed from the generator); the
         captures of the calls are gathered per prompt as _prompts_group leaves them."""
-        out_ids, segs, extras, caps = [], [], [[] for _ in range(self._extras())], []
+        out_ids, segs, extras, caps = [], [], [[] for _ in range(self._extras() + int(self._want_scores))], []
         keep = self.capture
         try:
             for ids in ids_list:
@@ -661,7 +680,10 @@ class VideoGLaMMForCausalLM:
         elif mode == "first":
             start()
         ctx = context_images[0] if context_images is not None else None
-        traces = [{} for _ in ids_list] if self.capture is not None else None
+        traces = [{} for _ in ids_list] if self.capture is not None or self._want_scores else None
+        if self._want_scores:
+            for t in traces:
+                t["scores"] = True
         out, emb, counts = generate_prompts(self.P, self._live_cfg(), self.towers, images[0].to(self.device),
                                             None if ctx is None else ctx.to(self.device), ids_list, max_new_tokens, self._eos(),
                                             token_hook=self.token_hook, samplings=samplings, traces=traces,
@@ -674,8 +696,9 @@ class VideoGLaMMForCausalLM:
         if self.capture is not None:
             self.capture["argmax"] = [t.get("argmax", []) for t in traces]
             self.capture["emb"] = [emb[a:a + n] for a, n in zip(starts, counts)]
+        scores = [[t["scores"] for t in traces]] if self._want_scores else []       # the last extra list: one record set per prompt
         if emb.shape[0] == 0:
-            return out, [{} for _ in ids_list], [[{} for _ in ids_list] for _ in range(self._extras())]
+            return out, [{} for _ in ids_list], [[{} for _ in ids_list] for _ in range(self._extras())] + scores
         hw = tuple(original_size_list[0])
         fast = self._fast_masks()
         if video:
@@ -693,14 +716,14 @@ class VideoGLaMMForCausalLM:
         stage_mark(self.stages, "propagation" if video else "mask_decode")
         # objects [a, a + n) are prompt b's, renumbered from 0; one list per extra return value (boxes, codes) follows the masks
         per = [self._result(*self._cut(*down, a, n)) if n else self._result(None) for a, n in zip(starts, counts)]
-        return out, [p[0][0] for p in per], [[p[i][0] for p in per] for i in range(1, 1 + self._extras())]
+        return out, [p[0][0] for p in per], [[p[i][0] for p in per] for i in range(1, 1 + self._extras())] + scores
 
     # ------------------------------------------------------------------ several clips, one prompt each
     def inference_clips(self, clips, max_new_tokens=32, use_sam2_video_branch=False, *, do_sample=None, temperature=None, top_k=None, top_p=None,
-                        generator=None, return_boxes=False, return_rle=False, return_masks=True):
+                        generator=None, return_boxes=False, return_rle=False, return_masks=True, return_scores=False):
         """B clips, one prompt each -> a list whose entry b is what inference(*clips[b], max_new_tokens, use_sam2_video_branch, ...) returns
         (with return_boxes: inference()'s third element, [{frame: {obj: np.float32[4]}}], in every clip's tuple; with return_rle its codes after
-        that; return_masks=False as in inference()):
+        that; return_masks=False as in inference(); with return_scores inference()'s [records] as the last element of every clip's tuple):
         (output ids [1, L_b + G_b], [{frame: {obj: mask}}]), the same ids and the same masks pixel for pixel.  clips[b]: the six per-clip arguments
         of inference() (images, context_images, images_for_sam, input_ids, resize_list, original_size_list) as a tuple or a dict.
         Every clip runs its own towers, Hiera and whole-prompt prefill; the clips of a group (up to 16) then decode together, one row per clip in
@@ -711,7 +734,7 @@ class VideoGLaMMForCausalLM:
         from .clips import as_clip, groups
         if self.comm is not None and self.comm.world > 1:
             raise NotImplementedError("inference_clips() runs on one GPU: call inference() per clip on a multi-GPU model")
-        self._set_returns(return_boxes, return_rle, return_masks)
+        self._set_returns(return_boxes, return_rle, return_masks, return_scores)
         clips = [as_clip(c, b) for b, c in enumerate(clips)]
         if not clips:
             raise NotImplementedError("inference_clips() needs at least one clip")
@@ -753,12 +776,14 @@ class VideoGLaMMForCausalLM:
             ctx = context_images[0] if context_images is not None else None
             text.append((images[0].to(self.device), None if ctx is None else ctx.to(self.device), input_ids[0].cpu()))
         first = mode in ("first", "serial")
+        traces = [{"scores": True} for _ in clips] if self._want_scores else None
         res = generate_clips(self.P, self._live_cfg(), self.towers, text, max_new_tokens, self._eos(), token_hook=self.token_hook,
-                             samplings=samplings, before_clip=start if first else None, after_prefill=None if first else start)
+                             samplings=samplings, traces=traces, before_clip=start if first else None, after_prefill=None if first else start)
         out = []
         for b, ((out_ids, emb), clip) in enumerate(zip(res, clips)):
             joins[b]()
-            out.append((out_ids.unsqueeze(0),) + self._clip_masks(sams.pop(b), emb, feats.pop(b), tuple(clip[5][0]), video))
+            tail = ([traces[b]["scores"]],) if self._want_scores else ()
+            out.append((out_ids.unsqueeze(0),) + self._clip_masks(sams.pop(b), emb, feats.pop(b), tuple(clip[5][0]), video) + tail)
         return out
 
     def _clip_masks(self, sam, emb, feats, hw, video):

@@ -997,6 +997,29 @@ def sample_partial_rows(logits, params, step, acc=None, tok=None, u_override=Non
     _lib.check(rc, "vg_sample_partial_rows")
 
 
+def token_scores_workspace(B, device):
+    """token_scores_rows' workspace for B rows: [B, vg_token_scores_workspace_ints()] int32, zero-filled once (row b works in slice b)"""
+    return torch.zeros(int(B), int(_lib.load().vg_token_scores_workspace_ints()), dtype=torch.int32, device=device)
+
+
+def token_scores_rows(logits, step, scores, top2, acc=None, tok=None, ws=None):
+    """per-token scores of the B rows of logits [B, V] (fp32, rows contiguous, B <= 16) in one launch (vg_token_scores_rows): slot step[b] of
+    scores[b] (float32 [B, cap, 2]) receives (log_softmax(row b)[pick], top-2 margin) and the same slot of top2[b] (int64 [B, cap, 2]) the
+    indices (top1, top2).  The pick is the index in the packed key acc[b] (argmax_partial's / sample_partial's hand-off, read only) or tok[b]:
+    exactly one of them (int64 [B]).  ws: token_scores_workspace(B), needed for V > 2048.  Row b is bit-identical to the launch on row b alone."""
+    lib = _lib.load()
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]
+    B, n = logits.shape
+    assert step.dtype == torch.int32 and step.is_contiguous() and step.numel() >= B
+    assert scores.dtype == torch.float32 and top2.dtype == torch.int64 and scores.is_contiguous() and top2.is_contiguous()
+    assert scores.shape == top2.shape and scores.numel() % (2 * B) == 0 and scores.shape[-1] == 2
+    cap = scores.numel() // (2 * B)
+    assert all(t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= B) for t in (acc, tok))
+    assert ws is None or (ws.dtype == torch.int32 and ws.is_contiguous() and ws.numel() >= B * lib.vg_token_scores_workspace_ints())
+    rc = lib.vg_token_scores_rows(_p(logits), logits.stride(0), n, B, _p(acc), _p(tok), _p(step), _p(scores), _p(top2), cap, _p(ws), _stream())
+    _lib.check(rc, "vg_token_scores_rows")
+
+
 def sample_survivors(x, params_dev):
     """the entries the warpers keep for one fp32 logits row (vg_sample_survivors) -> (indices int64, probabilities fp32), ascending index."""
     lib = _lib.load()

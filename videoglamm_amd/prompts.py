@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import ops
-from .vlm import IMAGE_TOKEN_INDEX, LlamaDecoder, RowsDecode, decode_loop, splice, stage_mark
+from .vlm import IMAGE_TOKEN_INDEX, LlamaDecoder, RowsDecode, decode_loop, read_scores, splice, stage_mark, wants_scores
 
 GROUP = 16       # prompts per pass; longer lists run in consecutive groups
 BUCKETS = (2, 4, 8, 16)     # rows of a captured batched decode step
@@ -76,7 +76,8 @@ def check_prompts(ids_list):
 def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_new_tokens, eos_token_id=None, token_hook=None,
                      samplings=None, traces=None, after_prefix=None, stages=None):
     """vlm.generate() for B prompts on one clip.  ids_list: host int64 [L_b] each, with an identical prefix up to the visual block
-    (check_prompts).  samplings[b]: None (greedy) or prompt b's dict(T, k, p, seed); traces[b]: optional dict per prompt (trace["argmax"]).
+    (check_prompts).  samplings[b]: None (greedy) or prompt b's dict(T, k, p, seed); traces[b]: optional dict per prompt (trace["argmax"];
+    trace["scores"] = True is replaced by the prompt's per-token records as in generate(), on the batched and on the sequential route).
     after_prefix: called once the prefix is prefilled (VG_HIERA_START=prefill); stages: generate()'s per-stage marks (towers, prefill, decode).
     -> (output ids host int64 [L_b + G_b] per prompt, pred_embeddings device [sum N_b, 256] in prompt order, N_b per prompt).
 
@@ -118,6 +119,10 @@ def generate_prompts(params, cfg, towers, images, context_images, ids_list, max_
             dec._rows.clear()          # one batched state per decoder: its slots are sized by the clip
             rows = dec._rows[key] = RowsDecode(dec, bucket(B), row0, n_bound)
         rows.route = routes[0]
+    scores = any(wants_scores(t) for t in (traces or []))
+    dec.set_scores(scores)
+    if rows is not None:
+        rows.set_scores(scores)
     out, embs, counts = [], [], []
     added = P - n0                     # "num_newly_added_tokens" (VideoGLaMM.py:613,786)
 
@@ -178,6 +183,7 @@ def decode_rows(rows, out, max_new_tokens, eos, token_hook=None, traces=None):
     max_new_tokens; replaced tokens go back in one copy; the step is replayed while any prompt is live."""
     B = len(out)
     live = [True] * B
+    n_prompt = [len(o) for o in out]
     for step in range(max_new_tokens):
         toks = rows.tok.cpu().tolist()
         repl_any = False
@@ -201,3 +207,9 @@ def decode_rows(rows, out, max_new_tokens, eos, token_hook=None, traces=None):
         if repl_any:
             rows.tok.copy_(torch.tensor(toks, dtype=torch.int64))
         rows.decode_step()
+    want = [b for b in range(B) if traces is not None and wants_scores(traces[b])]
+    if want:      # one read after the loop; every row is cut to the tokens it emitted itself
+        G = [len(out[b]) - n_prompt[b] for b in range(B)]
+        sc, t2 = rows.score_hist[:B, :max(G)].cpu(), rows.top2_hist[:B, :max(G)].cpu()
+        for b in want:
+            traces[b]["scores"] = read_scores(sc[b], t2[b], G[b])

@@ -493,6 +493,9 @@ class LlamaDecoder:
         # sampled decoding (vg_sample): None = greedy; else dict(T, k, p, seed), the values held in the device block samp_params that
         # the captured step reads — a new temperature / top-p / top-k / seed is a copy into it, never a re-capture
         self.sampling, self.samp_params, self.samp_ws, self.samp_fast = None, None, None, False
+        # per-token scores (vg_token_scores_rows): off by default; set_scores(True) makes every emitted token leave
+        # (logprob, margin) in score_hist and (top1, top2) in top2_hist, at the slot of its step
+        self.scores_on, self.score_hist, self.top2_hist, self.score_ws = False, None, None, None
         if self.dense_dropped:
             self._drop_dense_mlp()
 
@@ -537,6 +540,22 @@ class LlamaDecoder:
         ops.sampling_params(self.sampling["T"], self.sampling["k"], self.sampling["p"], self.sampling["seed"], self.P.device, out=self.samp_params)
         # the route is fixed by k: the multi-workgroup fast route for 1 <= k <= 64, the one-workgroup general route otherwise
         self.samp_fast = ops.sample_fast_route(self.sampling["k"], self.P.t("lm_head.weight").shape[0])
+
+    def set_scores(self, on):
+        """on: every emitted token also records its log-probability, top-2 margin and top-2 indices (ops.token_scores_rows) at slot *step_dev
+        of score_hist (float32 [HIST, 2]) / top2_hist (int64 [HIST, 2]); the step with scores is a captured graph of its own.  Off: the
+        launches, graph keys and buffers of a decoder that never heard of scores."""
+        self.scores_on = bool(on)
+        if self.scores_on and self.score_hist is None:
+            dev = self.P.device
+            self.score_hist = torch.zeros(self.HIST, 2, dtype=torch.float32, device=dev)
+            self.top2_hist = torch.zeros(self.HIST, 2, dtype=torch.int64, device=dev)
+            self.score_ws = ops.token_scores_workspace(1, dev)
+
+    def _record_scores(self, logits, acc=None, tok=None):
+        """the scores launch on the fp32 logits row [1, V] of the token being emitted (slot *step_dev)"""
+        ops.token_scores_rows(logits, self.step_dev, self.score_hist.view(1, self.HIST, 2), self.top2_hist.view(1, self.HIST, 2), acc=acc, tok=tok,
+                              ws=self.score_ws)
 
     def _layers(self, x, pos0, pos_dev, kv_hook=None):
         """decoder stack on x [S,D]; KV appended at pos (host value pos0, or *pos_dev when given).
@@ -714,8 +733,10 @@ class LlamaDecoder:
             logits = ops.linear(hidden_row, self.P.w("lm_head"), out_dtype=torch.float32)
         if self.sampling is not None:
             ops.sample_partial(logits[-1], self.samp_params, self.step_dev, tok=self.tok_dev, fast_ws=self.samp_ws if self.samp_fast else None)
-            return
-        ops.argmax(logits.view(1, -1), out=self.tok_dev)
+        else:
+            ops.argmax(logits.view(1, -1), out=self.tok_dev)
+        if self.scores_on:
+            self._record_scores(logits[-1:], tok=self.tok_dev)
 
     def _decode_step(self):
         """static step: consume tok_dev at position *pos_dev, emit the next token into tok_dev, advance pos_dev."""
@@ -736,6 +757,9 @@ class LlamaDecoder:
                                fast_ws=self.samp_ws if self.samp_fast else None)
         else:
             ops.argmax_partial(logits.view(-1), self.amax_acc)
+        if self.scores_on:
+            # *step_dev still names the token being emitted and amax_acc holds the model's own pick (decode_step_end forces, counts and clears)
+            self._record_scores(logits.view(1, -1), acc=self.amax_acc)
         ops.decode_step_end(self.amax_acc, self.tok_dev, self.pos_dev, self.step_dev, h, self.hid_all, self.forced, self.hist, self.raw)
 
     def advance(self, inc):
@@ -759,6 +783,8 @@ class LlamaDecoder:
             self.staged = min(self.staged, self.pos)       # row pos is appended to the e4m3 cache only
         # the route (greedy / fast / general sampler) is part of the captured launches; T, k, p and the seed are not
         key = self.kpw if self.sampling is None else (self.kpw, "sample_fast" if self.samp_fast else "sample")
+        if self.scores_on:
+            key = (key if isinstance(key, tuple) else (key,)) + ("scores",)
         self.graph = self.graphs.get(key)
         if not self.use_graph:
             self._decode_step()
@@ -833,10 +859,20 @@ class RowsDecode:
         else:
             self.attn_ws = ops.decode_attention2_rows_workspace(d.H, d.Hkv, d.hd, n_bound, d.kpw2, B, dev)
         self.route = "greedy"
+        self.scores_on, self.score_hist, self.top2_hist, self.score_ws = False, None, None, None      # set_scores
         self.graphs = {}
         self.steps = 0          # replayed (or eager) steps since the object was made: the batched loop's step count
         self.host_pos = [0] * B  # every row's position, known on the host: a step past n_bound is refused before it is launched
         self.start_pos = [0] * B  # the positions the rows were loaded at (load_row / pad_row)
+
+    def set_scores(self, on):
+        """LlamaDecoder.set_scores for the B rows: score_hist float32 / top2_hist int64 [B, HIST, 2], one ops.token_scores_rows launch per step"""
+        self.scores_on = bool(on)
+        if self.scores_on and self.score_hist is None:
+            dev = self.dec.P.device
+            self.score_hist = torch.zeros(self.B, self.dec.HIST, 2, dtype=torch.float32, device=dev)
+            self.top2_hist = torch.zeros(self.B, self.dec.HIST, 2, dtype=torch.int64, device=dev)
+            self.score_ws = ops.token_scores_workspace(self.B, dev)
 
     def load_row(self, b, P, end):
         """row b continues from the decoder's state after prompt b's suffix prefill and first token: its K / V rows [row0, end) and final-norm rows
@@ -855,6 +891,9 @@ class RowsDecode:
         self.forced[b].fill_(-1)
         if d.sampling is not None:
             self.samp_params[b].copy_(d.samp_params)
+        if self.scores_on:      # slot 0: the record the decoder's single-row step left for the prefill's token
+            self.score_hist[b, 0].copy_(d.score_hist[0])
+            self.top2_hist[b, 0].copy_(d.top2_hist[0])
 
     def pad_row(self, b, P, like=0):
         """a bucket row without a prompt: position P of its own slot, token 0, row `like`'s sampling block"""
@@ -893,6 +932,9 @@ class RowsDecode:
         else:
             # vg_sample for the B rows in one launch: every row its own parameter block, step counter, accumulator and (fast route) workspace
             ops.sample_partial_rows(logits, self.samp_params, self.step, acc=self.acc, fast_ws=self.samp_ws if self.route == "sample_fast" else None)
+        if self.scores_on:
+            # one launch for the B rows: step[b] still names the token row b emits, acc[b] holds the row's own pick
+            ops.token_scores_rows(logits, self.step, self.score_hist, self.top2_hist, acc=self.acc, ws=self.score_ws)
         ops.decode_step_end_rows(self.acc, self.tok, self.pos, self.step, h, self.hid, forced=self.forced, hist=self.hist, raw=self.raw,
                                  hid_row0=self.row0)
 
@@ -912,9 +954,10 @@ class RowsDecode:
         if not self.dec.use_graph:
             self._step()
             return
-        g = self.graphs.get(self.route)
+        key = (self.route, "scores") if self.scores_on else self.route
+        g = self.graphs.get(key)
         if g is None:
-            g = self.graphs[self.route] = capture_step(self._step, (self.tok, self.pos, self.step))
+            g = self.graphs[key] = capture_step(self._step, (self.tok, self.pos, self.step))
         g.replay()
 
     def rows_of(self, b, P, rows):
@@ -955,7 +998,9 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     emitted.  token_hook(step, token_id) -> token_id | None: called with every emitted token AFTER the full lm_head + argmax (the place of a
     logits processor in HF generate()); a returned id replaces the token (teacher forcing in tests; synth.forced_tokens_hook for the synthetic-weight
     benchmark, whose random weights never emit [SEG] — no work is skipped).
-    trace: optional dict; trace["argmax"] receives the model's own argmax of every step (before any forcing).
+    trace: optional dict; trace["argmax"] receives the model's own argmax of every step (before any forcing).  A caller that puts
+    trace["scores"] = True gets it replaced by {"logprob": float32 [G], "margin": float32 [G], "top2": int64 [G, 2]} (host numpy, G = generated
+    tokens): log_softmax of the raw logits at the model's own pick, the top-2 margin and the top-2 indices of every step.
     eos_token_id: one id or several (HF generate() stops on any id of generation_config.eos_token_id).
     sampling: None = greedy; dict(T=, k=, p=, seed=) = HF's do_sample decoding (Temperature -> TopK -> TopP, then a draw) on the device,
     token j drawn with the uniform of Philox counter j; trace["argmax"] then holds the drawn ids before forcing.
@@ -975,6 +1020,7 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     dec.check_dense(cfg["llm"])        # (a kept decoder does not follow the live cfg; after dense_mlp = "drop" a cfg that asks for a dense mode is refused, not ignored)
     dec.reset()
     dec.set_sampling(sampling)
+    dec.set_scores(wants_scores(trace))
     if comm is not None and comm.world > 1 and x.shape[0] >= 64 * comm.world and os.environ.get("VG_PREFILL_SHARDED", "0") == "1":
         hidden = dec.forward_sharded(x, comm)   # opt-in sequence-parallel prefill: 1/world of the rows per rank (row chunks of another
         #                                         M take other GEMM routes: bf16 ids may differ from the single-GPU run; default = replicated)
@@ -1004,9 +1050,26 @@ def generate(params, cfg, towers, images, context_images, input_ids, max_new_tok
     return out_ids, emb
 
 
+def wants_scores(trace):
+    """True for a trace dictionary whose caller put trace["scores"] = True (generate() replaces it by the records)"""
+    return trace is not None and trace.get("scores") is True
+
+
+def read_scores(score_hist, top2_hist, G):
+    """the records of the first G emitted tokens of one row (score_hist float32 [HIST, 2], top2_hist int64 [HIST, 2]), read back once ->
+    {"logprob": float32 [G], "margin": float32 [G], "top2": int64 [G, 2]} as host numpy arrays"""
+    import numpy as np
+    if G <= 0:
+        return {"logprob": np.zeros(0, np.float32), "margin": np.zeros(0, np.float32), "top2": np.zeros((0, 2), np.int64)}
+    sc, t2 = score_hist[:G].cpu().numpy(), top2_hist[:G].cpu().numpy()
+    return {"logprob": sc[:, 0].copy(), "margin": sc[:, 1].copy(), "top2": t2.copy()}
+
+
 def decode_loop(params, dec, ids, max_new_tokens, eos, token_hook=None, trace=None):
     """generate()'s token loop from the token the prefill emitted (dec.next_token already enqueued): appends the emitted ids to the host list
-    `ids` until an id of `eos` or max_new_tokens; dec's hid_all then holds the final-norm row of every decoded position."""
+    `ids` until an id of `eos` or max_new_tokens; dec's hid_all then holds the final-norm row of every decoded position.  A trace that asks for
+    scores (wants_scores; the caller has switched dec.set_scores on before the first token) receives the records of the emitted tokens."""
+    n_prompt = len(ids)
     # The loop.  Forcing / recording / the position bump can happen on the device (LlamaDecoder.advance), so with no Python hook in the way step k + 1
     # can be enqueued BEFORE token k is read back (VG_DECODE_AHEAD=1: tokens return on a side stream behind per-step events; the step launched while
     # an EOS token was in flight is wasted — it writes cache rows past the end that nobody reads).  Built for VERDICT r05 item 1(c) and measured r06 on C2
@@ -1069,6 +1132,8 @@ def decode_loop(params, dec, ids, max_new_tokens, eos, token_hook=None, trace=No
             if nxt in eos or step == max_new_tokens - 1:
                 break
             dec.decode_step()
+    if wants_scores(trace):      # one read after the loop, cut to the tokens this prompt emitted
+        trace["scores"] = read_scores(dec.score_hist, dec.top2_hist, len(ids) - n_prompt)
     if dec.chain_roles and dec.chain_flags is not None and int(dec.chain_err) + int(dec.chain_flags[:, 1].sum()):
         # VG_DECODE_CHAIN: a workgroup of a chained layer launch stopped waiting for its producer role (bounded wait) — the ids above are not to be trusted
         raise ops._lib.VGKernelError("vg_decode_layer: a device-side wait gave up (flags[1] set); rerun with VG_DECODE_CHAIN=0")

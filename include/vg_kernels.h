@@ -688,6 +688,22 @@ int vg_mask_pair_counts(const uint8_t* a, const uint8_t* b, int64_t* inter, int6
  * R/eval_referdavis_metrics.py:194-259.  fg, gt: uint8 [N,H,W]. */
 int vg_boundary_counts(const uint8_t* fg, const uint8_t* gt, int64_t* out, int N, int H, int W, int radius,
                        vg_stream_t stream);
+/* The class counts of the validation metrics (gIoU / cIoU) from mask LOGITS, all N masks of a call in one pass:
+ * intersectionAndUnionGPU(output = (logit > 0), target, K = 2, ignore_index), R/utils/utils.py:78-90, as the validator
+ * calls it per frame (R/utils/trainer.py:443-447).  logits: [N, L] of dtype VG_F32 | VG_BF16, contiguous; target: [N, L]
+ * uint8; out: int64 [N, 6] = {inter0, inter1, out0, out1, tgt0, tgt1}.
+ *   - the predicted class of a pixel is logit > 0, strictly: 0.0, -0.0, NaN and -inf are class 0, +inf and the smallest
+ *     positive denormal are class 1; in bf16 the comparison is on the stored value;
+ *   - a pixel whose target equals ignore_index counts in nothing;
+ *   - every other pixel counts in out[class]; if its target t is 0 or 1 also in tgt[t], and in inter[t] if class == t;
+ *   - so a target value that is neither 0, 1 nor ignore_index counts in out only (histc with min = 0, max = 1 drops it).
+ * The union is not an output: the caller forms out + tgt - inter.  Accumulators are int64 and pixel indices 64-bit
+ * (L may pass 2^31; L < 2^40); integer sums: the result does not depend on the order of the reduction.  out is fully
+ * written by the call (no memset by the caller, no dependence on its previous contents).  The inputs need no alignment
+ * beyond their element size: an odd L or an odd row start is legal.  N <= 65535.  VG_ERR_ARG before any launch: a null
+ * pointer, N <= 0, L <= 0, a dtype that is neither VG_F32 nor VG_BF16, ignore_index outside 0..255. */
+int vg_logit_class_counts(const void* logits, const uint8_t* target, int64_t* out, int N, int64_t L, int dtype,
+                          int ignore_index, vg_stream_t stream);
 /* out[n] = {xmin, ymin, xmax, ymax, area} (int32 [N,5]) of mask n of mask:[N,H,W] uint8 (foreground = nonzero); the
  * maxima are INCLUSIVE pixel indices, an empty mask gives {W, H, -1, -1, 0}.  The integer part of masks_to_boxes,
  * R/utils/grounding_utils/box_ops.py:118-142.  All N masks in one call; out is fully written by the call (no memset

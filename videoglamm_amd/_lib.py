@@ -137,6 +137,7 @@ def _sig(lib):
         "vg_fill_holes": ([P, P, P, P, I, I, I, I, P], c_int),
         "vg_mask_pair_counts": ([P, P, P, P, I, I, L, I, P], c_int),
         "vg_boundary_counts": ([P, P, P, I, I, I, I, P], c_int),
+        "vg_logit_class_counts": ([P, P, P, I, L, I, I, P], c_int),
         "vg_mask_boxes": ([P, P, I, I, I, P], c_int),
         "vg_blob_boxes": ([P, P, P, P, P, I, I, I, I, P], c_int),
         "vg_mask_rle_units": ([I, I], c_int),

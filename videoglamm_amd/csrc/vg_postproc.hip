@@ -569,6 +569,90 @@ __global__ __launch_bounds__(1024) void cc_boxes_kernel(CCArgs p, int32_t* boxes
   box_commit<16>(xmin, ymin, xmax, ymax, area, boxes + (int64_t)blockIdx.y * 5);
 }
 
+// ---------------------------------------------------------------------------------------------- class counts from logits
+// The validator's intersectionAndUnionGPU(logit > 0, target, K = 2, ignore_index) (R/utils/utils.py:78-90) for all N masks
+// of a call in one pass: 4 or 2 bytes of logit and 1 byte of target per pixel.  A thread takes groups of 16 pixels: the
+// logits in 16-byte loads from the first 16-byte boundary of the mask's logits on (`head` pixels in front of it and the
+// < 16 behind the last whole group go pixel by pixel, workgroup 0 of the mask), the 16 target bytes in one load at
+// whatever alignment that leaves them.  Everything is counted on byte masks (0x80 per pixel of a target dword).
+//
+// "logit > 0" is decided on the BITS: positive, not zero, not NaN <=> bits - 1 < 0x7f800000 (0x7f80 for bf16) as unsigned.
+// No floating-point compare, so the smallest denormal is class 1 whatever the kernel's denormal mode is.
+__device__ __forceinline__ bool lcc_pos(float v) { return __float_as_uint(v) - 1u < 0x7f800000u; }
+__device__ __forceinline__ bool lcc_pos(bf16_t v) { return (uint32_t)v - 1u < 0x7f80u; }
+
+struct LccCounts {
+  uint32_t nv, o1, t0, t1, i0, i1;      // not ignored; of those: class 1, target 0, target 1, target 0 & class 0, target 1 & class 1
+};
+
+// v: four target bytes, P: 0x80 in the byte of every pixel of class 1, ign4: the ignore label in all four bytes
+__device__ __forceinline__ void lcc_count4(LccCounts& c, uint32_t v, uint32_t P, uint32_t ign4) {
+  const uint32_t V = nz_bytes(v ^ ign4);
+  const uint32_t Z = ~nz_bytes(v) & V, O = ~nz_bytes(v ^ 0x01010101u) & V;
+  c.nv += __popc(V);
+  c.o1 += __popc(V & P);
+  c.t0 += __popc(Z);
+  c.t1 += __popc(O);
+  c.i0 += __popc(Z & ~P);
+  c.i1 += __popc(O & P);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void logit_class_counts_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target,
+                                                                 unsigned long long* __restrict__ out, int64_t L, uint32_t ign) {
+  constexpr int PER = 16 / sizeof(T);       // logits per 16-byte load: 4 (fp32) or 8 (bf16)
+  const int n = blockIdx.y;
+  const T* pl = logits + (int64_t)n * L;
+  const uint8_t* pt = target + (int64_t)n * L;
+  const int64_t head = min(L, (int64_t)(((16 - ((uintptr_t)pl & 15)) & 15) / sizeof(T)));
+  const int64_t nw = (L - head) >> 4;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+  const uint32_t ign4 = ign * 0x01010101u;
+  LccCounts c = {0, 0, 0, 0, 0, 0};       // a thread sees fewer than 2^32 pixels: L < 2^40 and >= 16 workgroups per mask of that size
+  for (int64_t w = tid; w < nw; w += nth) {
+    const int64_t i = head + 16 * w;
+    u32x4_t lv[16 / PER], tv;
+#pragma unroll
+    for (int k = 0; k < 16 / PER; ++k) lv[k] = __builtin_nontemporal_load((const u32x4_t*)(pl + i) + k);
+    __builtin_memcpy(&tv, pt + i, 16);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {           // target dword d = pixels 4 d .. 4 d + 3
+      uint32_t P = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int e = 4 * d + b;
+        bool pos;
+        if constexpr (sizeof(T) == 4) pos = lv[e / 4][e % 4] - 1u < 0x7f800000u;
+        else pos = ((lv[e / 8][(e % 8) / 2] >> (16 * (e & 1))) & 0xffffu) - 1u < 0x7f80u;
+        P |= pos ? 0x80u << (8 * b) : 0u;
+      }
+      lcc_count4(c, tv[d], P, ign4);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 32) {           // the ends: at most 15 pixels each
+    const int64_t tail0 = head + 16 * nw;
+    const int64_t i = threadIdx.x < 16 ? threadIdx.x : tail0 + threadIdx.x - 16;
+    if (threadIdx.x < 16 ? i < head : i < L) lcc_count4(c, pt[i] | (ign4 & 0xffffff00u), lcc_pos(pl[i]) ? 0x80u : 0u, ign4);
+  }
+  // registers -> wave -> LDS -> at most six 64-bit device atomics per workgroup, none for a zero.  Integer sums: any
+  // arrival order gives the same table.
+  unsigned long long v[6] = {(unsigned long long)c.i0, c.i1, (unsigned long long)c.nv - c.o1, c.o1, c.t0, c.t1};
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_xor(v[k], s, 64);
+  __shared__ unsigned long long red[6][4];
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) red[k][threadIdx.x >> 6] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const unsigned long long t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    if (t) atomicAdd(out + (int64_t)n * 6 + threadIdx.x, t);
+  }
+}
+
 int box_init(int32_t* out, int N, int H, int W, hipStream_t st) {
   box_init_kernel<<<(N + 255) / 256, 256, 0, st>>>(out, N, H, W);
   VG_LAUNCH_CHECK();
@@ -929,6 +1013,30 @@ extern "C" int vg_boundary_counts(const uint8_t* fg, const uint8_t* gt, int64_t*
     return VG_ERR_LAUNCH;
   }
   boundary_counts_kernel<<<dim3((W + 63) / 64, (H + 63) / 64, N), 256, 0, st>>>(fg, gt, (unsigned long long*)out, H, W, radius);
+  VG_LAUNCH_CHECK();
+  return VG_OK;
+}
+
+extern "C" int vg_logit_class_counts(const void* logits, const uint8_t* target, int64_t* out, int N, int64_t L, int dtype,
+                                     int ignore_index, vg_stream_t stream) {
+  VG_CHECK(logits && target && out, VG_ERR_ARG, "vg_logit_class_counts: null pointer");
+  VG_CHECK(N > 0 && N <= 65535 && L > 0 && L < (1ll << 40), VG_ERR_ARG, "vg_logit_class_counts: bad shape N=%d L=%lld", N, (long long)L);
+  VG_CHECK(dtype == VG_F32 || dtype == VG_BF16, VG_ERR_ARG, "vg_logit_class_counts: dtype %d is neither VG_F32 nor VG_BF16", dtype);
+  VG_CHECK(ignore_index >= 0 && ignore_index <= 255, VG_ERR_ARG, "vg_logit_class_counts: ignore_index %d not in [0, 255]", ignore_index);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, sizeof(int64_t) * 6 * N, st) != hipSuccess) {
+    vg_set_error("vg_logit_class_counts: memset failed");
+    return VG_ERR_LAUNCH;
+  }
+  // workgroups per mask: >= 4 groups of 16 pixels per thread, 2048 workgroups over the batch, between 16 and 256 per mask
+  const int64_t units = (L / 16 + 1023) / 1024;
+  const int cap = 2048 / N < 16 ? 16 : (2048 / N > 256 ? 256 : 2048 / N);
+  const int chunks = (int)(units < 1 ? 1 : (units > cap ? cap : units));
+  const dim3 grid(chunks, N);
+  if (dtype == VG_BF16)
+    logit_class_counts_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)logits, target, (unsigned long long*)out, L, (uint32_t)ignore_index);
+  else
+    logit_class_counts_kernel<float><<<grid, 256, 0, st>>>((const float*)logits, target, (unsigned long long*)out, L, (uint32_t)ignore_index);
   VG_LAUNCH_CHECK();
   return VG_OK;
 }

@@ -291,6 +291,21 @@ class VideoGLaMMForCausalLM:
         logits, _ = self.sam2.framewise_branch(images_for_sam[0].to(self.device), emb, hw)
         return {"pred_masks": [[logits[t] for t in range(logits.shape[0])]], "gt_masks": masks_list}
 
+    def validate(self, samples, ignore_index=255):
+        """The validator's loop (R/utils/trainer.py:409-473) over `samples`, an iterable of the keyword dictionaries model_forward takes
+        (masks_list = [ground truth [N, T, H, W] of 0 / 1 / ignore_index]): per sample model_forward(inference=True), the class counts of all
+        its frames from ONE launch on the logits where they are (postproc.validation_record), and the validator's meters on the host.
+        Returns (giou, ciou).  One GPU only."""
+        if self.comm is not None:
+            raise NotImplementedError("validate() runs on one GPU: the frames of a multi-GPU model are sharded over the ranks; "
+                                      "call model_forward() and postproc.validation_record on one GPU")
+        from . import postproc
+
+        meter = postproc.ValidationMeter()
+        for kw in samples:
+            meter.update(postproc.validation_record(self.model_forward(**dict(kw, inference=True)), ignore_index))
+        return meter.result()
+
     # ------------------------------------------------------------------ inference surface
     def inference(self, images, context_images, images_for_sam, input_ids, resize_list, original_size_list,
                   max_new_tokens=32, use_sam2_video_branch=False, *, return_boxes=False, return_rle=False, return_masks=True, return_scores=False,

@@ -1776,6 +1776,26 @@ def mask_boxes(masks, min_size=0, return_mask=False):
     return (out, kept) if return_mask else out
 
 
+def logit_class_counts(logits, target, ignore_index=255):
+    """logits [..., H, W] float32 / bf16, target of the same shape (bool, uint8 or an integer dtype with values in 0..255) ->
+    int64 [..., 6] = (inter0, inter1, out0, out1, tgt0, tgt1) per mask: the counts of the reference's
+    intersectionAndUnionGPU(logits > 0, target, K=2, ignore_index) for every leading index, in one launch
+    (vg_logit_class_counts; the contract is stated at its declaration).  The union is out + tgt - inter."""
+    lib = _lib.load()
+    assert logits.dtype in (torch.float32, torch.bfloat16), f"logits are float32 / bfloat16, got {logits.dtype}"
+    assert logits.dim() >= 2 and logits.shape == target.shape, f"logits {tuple(logits.shape)} and target {tuple(target.shape)} differ in shape"
+    if target.dtype not in (torch.bool, torch.uint8):
+        assert not target.dtype.is_floating_point and not target.dtype.is_complex, f"targets are bool / integer labels, got {target.dtype}"
+        assert target.numel() == 0 or bool(((target >= 0) & (target <= 255)).all()), "target labels must lie in 0..255"
+        target = target.to(torch.uint8)
+    x, t = logits.contiguous(), _u8(target)
+    L = x.shape[-2] * x.shape[-1]
+    N = x.numel() // L if L else 0
+    out = torch.empty(tuple(x.shape[:-2]) + (6,), dtype=torch.int64, device=x.device)
+    _lib.check(lib.vg_logit_class_counts(_p(x), _p(t), _p(out), N, L, _dt(x), int(ignore_index), _stream()), "vg_logit_class_counts")
+    return out
+
+
 def mask_rle(masks):
     """masks [..., H, W] bool/uint8 -> (counts int32 [total], offsets int64 [prod(lead) + 1]): COCO's uncompressed run-length
     code of every mask in mask_to_rle_pytorch's form (column-major pixel order, a leading 0 when pixel 0 is foreground); mask n's

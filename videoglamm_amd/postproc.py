@@ -15,6 +15,10 @@ pairing of compute_miou, the F formula) is the reference's float64 host arithmet
   np_box_area / np_box_iou     R/utils/grounding_utils/box_ops.py:12-62     (the reference's numpy arithmetic, on the host)
   calc_tiou                    R/eval_grounding.py:55-72                    (_calc_tiou)
   video_grounding_metrics      R/eval_grounding.py:326-405                  (the per-video record of the VidSTG / HC-STVG driver)
+  intersectionAndUnionGPU      R/utils/utils.py:78-90                       (K = 2; no write into `output`)
+  validation_counts / validation_record / ValidationMeter
+                               R/utils/trainer.py:413-465                   (the validator's gIoU / cIoU; the fused counts, N > 1
+                               objects and the single-process meter are this build's forms)
   mask_to_rle_pytorch / rle_to_mask / area_from_rle / coco_encode_rle
                                R/model/segment_anything_2/sam2/utils/amg.py:109-155, 296-302   (coco_decode_rle, the compressed string
                                as input and device= are this build's extensions; the string codec is pycocotools' rule, in Python)
@@ -224,6 +228,103 @@ def video_grounding_metrics(pred_boxes, gt_boxes, gt_sted, frame_ids, pred_sted=
     rec["gt_viou"] = gt_viou
     rec.update({f"gt_viou@{t}": int(gt_viou > t) for t in iou_thresholds})
     return rec
+
+
+# ---------------------------------------------------------------- validation (gIoU / cIoU): class counts from logits, ignore label included
+def _labels_u8(target):
+    """a ground truth as the validator holds it (bool, integer, or float labels it would .int()) -> device tensor that
+    ops.logit_class_counts takes: bool / uint8 as they are, anything else as integers (range-checked there)"""
+    t = _dev(target)
+    if t.dtype in (torch.bool, torch.uint8):
+        return t
+    return t.long() if t.dtype.is_floating_point else t
+
+
+def intersectionAndUnionGPU(output, target, K, ignore_index=255):
+    """Label tensors (0 / 1 in output, 0 / 1 / ignore_index in target) of 1 to 3 dimensions -> (area_intersection, area_union,
+    area_target), float32 device tensors [K], the values the reference returns for float input.  K must be 2.  Runs on
+    vg_logit_class_counts: the labels go in as float32 logits, output > 0 being the label for labels 0 / 1 (any other value in
+    output is outside this function's domain).  The reference also WRITES ignore_index into `output` where the target has it
+    (its callers pass a clone); that side effect is not reproduced: `output` is left as it is."""
+    if K != 2:
+        raise NotImplementedError(f"intersectionAndUnionGPU: K = {K}; the validator's two classes (K = 2) are what the kernel counts")
+    assert len(output.shape) in [1, 2, 3]
+    assert tuple(output.shape) == tuple(target.shape)
+    out = _dev(output)
+    if out.numel() == 0:
+        z = torch.zeros(2, dtype=torch.float32, device=out.device)
+        return z, z.clone(), z.clone()
+    c = ops.logit_class_counts(out.reshape(1, -1).to(torch.float32), _labels_u8(target).reshape(1, -1), ignore_index)
+    inter, area_out, area_tgt = c[0:2], c[2:4], c[4:6]
+    return inter.to(torch.float32), (area_out + area_tgt - inter).to(torch.float32), area_tgt.to(torch.float32)
+
+
+def validation_counts(pred_logits, gt_masks, ignore_index=255):
+    """The fused path of the validator's metric: mask logits [N, T, H, W] or [T, H, W] (float32 / bf16, on the device) and the
+    ground truth of the same shape (0 / 1 / ignore_index) -> int64 [.., T, 6] = (inter0, inter1, out0, out1, tgt0, tgt1) per
+    frame, all frames and objects in ONE launch: no thresholded copy, no clone, no histograms."""
+    if pred_logits.dim() not in (3, 4) or tuple(pred_logits.shape) != tuple(gt_masks.shape):
+        raise ValueError(f"validation_counts: logits {tuple(pred_logits.shape)} and ground truth {tuple(gt_masks.shape)} must be equal "
+                         "[N, T, H, W] or [T, H, W] shapes")
+    return ops.logit_class_counts(pred_logits, _labels_u8(gt_masks), ignore_index)
+
+
+def record_from_counts(table):
+    """The validator's per-sample arithmetic (R/utils/trainer.py:442-453) on a host table [T, 6] or [N, T, 6] of
+    validation_counts: (intersection float32 [2], union float32 [2], acc_iou float32 [2], n).  In the reference's float32
+    and in its order: per frame intersection += inter_i, union += union_i, acc_iou += inter_i / (union_i + 1e-5), + 1.0
+    where union_i == 0 (no-object target); acc_iou / n at the end.  The N * T (object, frame) rows of an [N, T, 6] table
+    enter alike, object-major, and n = N * T; for N = 1 that is the reference's value."""
+    c = torch.as_tensor(np.asarray(table)).reshape(-1, 6)
+    n = c.shape[0]
+    inter = c[:, 0:2].to(torch.float32)
+    uni = (c[:, 2:4] + c[:, 4:6] - c[:, 0:2]).to(torch.float32)
+    intersection, union, acc_iou = torch.zeros(2), torch.zeros(2), torch.zeros(2)
+    for inter_i, union_i in zip(inter, uni):
+        intersection += inter_i
+        union += union_i
+        acc_iou += inter_i / (union_i + 1e-5)
+        acc_iou[union_i == 0] += 1.0
+    return intersection.numpy(), union.numpy(), acc_iou.numpy() / n, n
+
+
+def validation_record(output_dict, ignore_index=255):
+    """R/utils/trainer.py:413-456 for one sample of model_forward(inference=True): pred_masks[0] (T tensors [N, H, W] of
+    logits) stacked to [N, T, H, W] on the device, gt_masks[0] ([N, T, H, W]; 0 / 1 / ignore_index), one validation_counts
+    call, one download of N * T * 48 bytes, record_from_counts.  Returns (intersection, union, acc_iou, n).
+    The reference asserts one object; N > 1 is this build's extension (record_from_counts).  A prediction without objects
+    (the [0, H, W] tensors model_forward returns when no [SEG] was emitted) counts as all-background logits for every object
+    of the ground truth: the reference would fail on it, and a missed object is what the metric should charge."""
+    gt = _labels_u8(output_dict["gt_masks"][0])
+    pred = torch.stack(list(output_dict["pred_masks"][0]), dim=0).permute(1, 0, 2, 3)
+    if pred.shape[0] == 0:
+        pred = torch.zeros(gt.shape, dtype=torch.float32, device=gt.device)
+    return record_from_counts(validation_counts(pred, gt, ignore_index).cpu().numpy())
+
+
+class ValidationMeter:
+    """The three meters of the validator (R/utils/trainer.py:454-465 over R/utils/utils.py AverageMeter) in one object, on the
+    host, one process (no all_reduce): update(record) takes what validation_record returns, result() gives (giou, ciou) =
+    (acc_iou_sum / count)[1], (intersection_sum / (union_sum + 1e-10))[1].  The sums keep the dtype numpy gives the
+    reference's own expressions (val * n added to a Python 0), which is the records' float32."""
+
+    def __init__(self):
+        self.intersection_sum = self.union_sum = self.acc_iou_sum = 0
+        self.count = 0
+
+    def update(self, record):
+        intersection, union, acc_iou, n = record
+        self.intersection_sum += intersection * 1
+        self.union_sum += union * 1
+        self.acc_iou_sum += acc_iou * n
+        self.count += n
+
+    def result(self):
+        if self.count == 0:
+            raise ValueError("ValidationMeter.result() before any update()")
+        iou_class = self.intersection_sum / (self.union_sum + 1e-10)
+        acc_iou_avg = self.acc_iou_sum / self.count
+        return float(acc_iou_avg[1]), float(iou_class[1])
 
 
 # ---------------------------------------------------------------- run-length codes (COCO RLE): the form masks are stored and exchanged in

@@ -506,7 +506,7 @@ int vg_rope_axial_heads(void* x, int64_t ld, int64_t sb, const float* cos, const
 /* out[i,:] = table[ids[i],:]   (nn.Embedding) */
 int vg_embed(const int64_t* ids, const void* table, void* out, int64_t n, int D, int dtype,
              vg_stream_t stream);
-/* out[r] = first index of the row maximum (torch.argmax)  x:[rows,n] */
+/* out[r] = first index of the row maximum (torch.argmax) (-0 counts as +0)  x:[rows,n] */
 int vg_argmax(const void* x, int64_t rows, int n, int64_t* out, int dtype, vg_stream_t stream);
 
 /* SAM2 mask selection, one call per decoder batch: masks fp32 [N,4,HW], ious fp32 [N,4], tokens [N,4,C].

@@ -359,7 +359,7 @@ extern "C" int vg_rmsnorm(const void* x, int64_t ldx, const float* w, void* y, i
 
 // argmax over long rows (lm_head logits, 128k entries): up to 64 workgroups per row atomicMax a packed
 // (order-preserving value bits, ~index) key into out[row] (zeroed first), then the key is decoded in place.
-// Ties -> lowest index, NaN-free inputs assumed (torch.argmax semantics on finite logits).
+// Ties -> lowest index (-0 ties with +0: the caller canonicalises the value it loads), NaN-free inputs assumed (torch.argmax semantics).
 __device__ __forceinline__ uint64_t amax_key(float v, int i) {
   uint32_t u = __float_as_uint(v);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone map of float order onto unsigned order
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void argmax_stage1(const void* __restrict__ x,
   const int64_t row = blockIdx.y;
   uint64_t best = 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += nb * 256) {
-    const uint64_t k = amax_key(ld_any(x, row * n + i, dt), i);
+    const uint64_t k = amax_key(ld_any(x, row * n + i, dt) + 0.f, i);   // v + 0: -0 counts as +0, as a float comparison has it
     best = k > best ? k : best;
   }
 #pragma unroll

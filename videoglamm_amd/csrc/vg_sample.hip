@@ -3,7 +3,7 @@
 // acc[0], so vg_decode_step_end consumes it unchanged.
 //
 // Contract (transformers 4.41 _get_logits_warper + _sample):
-//   y = x / T (a true fp32 division); top-k keeps every entry >= the k-th largest y (ties at the threshold all kept, k = 0 or k >= n: off);
+//   y = x / T (a true fp32 division; -0 counts as +0); top-k keeps every entry >= the k-th largest y (ties at the threshold all kept, k = 0 or k >= n: off);
 //   top-p (p < 1) keeps, in descending order, the entries whose probability mass ABOVE them is < p (the largest always kept);
 //   the token is the inverse CDF of softmax(kept) at u, walking the kept entries by descending y, ties by ascending index;
 //   u = (philox4x32_10(key = seed, counter = (step, 0, 0, 0))[0] >> 8) * 2^-24.
@@ -100,9 +100,9 @@ __device__ __forceinline__ void each(const SampleLds& s, bool cand, const float*
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = x[i + u * NT];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) f(v[u] / T, i + u * NT);
+      for (int u = 0; u < 4; ++u) f(v[u] / T + 0.f, i + u * NT);     // y + 0: -0 counts as +0, as HF's float comparisons have it
     }
-    for (; i < n; i += NT) f(x[i] / T, i);
+    for (; i < n; i += NT) f(x[i] / T + 0.f, i);
   }
 }
 
@@ -382,7 +382,7 @@ __device__ __forceinline__ void sample_fast(SampleLds& s, const float* __restric
 #pragma unroll
   for (int u = 0; u < FPT; ++u) {
     const int i = lo + tid + u * FT;
-    y[u] = i < hi ? x[i] / T : -INFINITY;
+    y[u] = i < hi ? x[i] / T + 0.f : -INFINITY;     // (-0 counts as +0, as in each())
     kv[u] = i < hi ? okey(y[u]) : 0u;     // 0 is below every real key: out-of-slice entries never win a bin
   }
   const int len = hi > lo ? hi - lo : 0;
